@@ -20,6 +20,13 @@ exchanges with RCCL on the tree's stream, all-reduced time-step limits), so
 the per-GPU work shrinks as N grows ("scaling": "strong"). A barrier
 brackets the timed region and the time is the max over ranks. `--replicas`
 runs one independent copy of the workload per GPU instead ("weak").
+
+A plain run sets up, warms up, times --steps unit steps and prints the result
+line (ms_per_step: one timed step). --dump-outputs DIR then writes the last
+timed step's outputs as DIR/<name>.npy; the inputs are the same in every run
+with the same arguments. --full adds what takes runs of its own: the
+dominant kernels' roofline lines, config 1's level-1 share and the CPU
+baseline.
 """
 import argparse
 import json
@@ -320,6 +327,53 @@ def write_topology(case, config, path, faces_from_phi=False, fused_rhs=False):
                    "fused_rhs": bool(fused_rhs)}, f)
 
 
+# --dump-outputs: bytes of all its files together (the limit is 64 MB)
+DUMP_BYTES = 48 << 20
+
+
+def step_outputs(case, s_out):
+    """{name: cell variable} of what a unit step into state s_out leaves its
+    caller: the species densities of that state, the potential and |E|."""
+    if isinstance(case, DriverCase):
+        sim = case.sim
+        ivs = [sim.species_itree[n] + s_out for n in sim.plasma] + [sim.i_phi, sim.i_efld]
+        return {str(sim.cc_names[iv - 1]).strip(): iv for iv in ivs}
+    from afh.streamer import IV
+    out = {sp: IV[sp] + s_out for sp in ("e", "pos", "neg")}
+    out["phi"], out["electric_fld"] = IV["phi"], IV["efld"]
+    return out
+
+
+def dump_outputs(case, s_out, last, path):
+    """--dump-outputs: path/<name>.npy (float64) for every variable of
+    step_outputs, and step_scalars.npy: the V-cycle residual(s) and dt limits
+    the last step returned, when it returned any (a Heun stage 1 returns
+    none). A tree whose leaves' interior cells exceed DUMP_BYTES is sampled:
+    the same seeded cells of the leaves in every variable and every run."""
+    topo, tree = case.topo, case.tree
+    nc, ndim = int(topo["nc"]), int(topo.get("ndim", 3))
+    leaves = np.sort(np.concatenate([np.asarray(topo["lvl_leaves_%d" % l], np.int64)
+                                     for l in range(1, int(topo["highest_lvl"]) + 1)])) - 1
+    names = step_outputs(case, s_out)
+    n_max = DUMP_BYTES // (8 * len(names))
+    cell = None
+    if len(leaves) * nc ** ndim > n_max:
+        rng = np.random.default_rng(20240229)
+        cell = (leaves[rng.integers(0, len(leaves), n_max)],) + tuple(
+            rng.integers(1, nc + 1, n_max) for _ in range(ndim))
+    os.makedirs(path, exist_ok=True)
+    interior = (slice(None),) + (slice(1, nc + 1),) * ndim
+    for name, iv in names.items():
+        a = tree.get_cc(iv)
+        a = a[cell] if cell is not None else a[leaves][interior]
+        fname = "".join(ch if ch.isalnum() or ch in "+-_" else "_" for ch in name)
+        np.save(os.path.join(path, fname + ".npy"), np.ascontiguousarray(a, np.float64))
+    res, lim = last if last is not None else ((), None)
+    scalars = [float(x) for x in res] + ([] if lim is None else [float(x) for x in np.ravel(lim)])
+    if scalars:
+        np.save(os.path.join(path, "step_scalars.npy"), np.array(scalars, np.float64))
+
+
 def _hip_stream():
     """A HIP stream shared by the thread ranks of --shared-stream."""
     import ctypes as C
@@ -501,6 +555,92 @@ def _roctx():
     return lib
 
 
+def kernel_lines(args, lib, case, dt, graphs, two_d, sharded):
+    """--full, after the timed region: the HIP-event times (afh_profile_*) of
+    the kernels the roofline lines are about, over eager unit steps of their
+    own where the timed region could not hold the events. Returns the
+    smoother's (ms, launches, bytes), its name, whether it was timed after
+    the timed region, the 2-D level-1 solve's ms per step and the fused
+    species step's (ms, launches, bytes) or None."""
+    import ctypes as C
+    from afh import capi
+    if graphs or two_d:
+        lib.call("profile_enable", case.tree.h, capi.PROF_GSRB if two_d else capi.PROF_GSRB_PAIR)
+        for k in range(2):
+            unit_step(case, dt, args.warmup + args.steps + k)
+        case.tree.sync()
+    ms, nl, by = C.c_double(), C.c_int64(), C.c_double()
+    lib.call("profile_read", case.tree.h, C.byref(ms), C.byref(nl), C.byref(by))
+    kname = ("k_gsrb_pair2<%d,%d>" % (CONFIGS[args.config][0], CONFIGS[args.config][0])
+             if CONFIGS[args.config][0] > 16 else "k_gsrb_pair_box<%d>" % CONFIGS[args.config][0])
+    if two_d:
+        kname = ("k2_pair_box (red+black pair, levels of >= 256 boxes, 24 B/cell)"
+                 if os.environ.get("AFH_PAIR2D", "1") != "0" else
+                 "k2_gsrb (half sweep, levels of >= 256 boxes, 16 B/cell)")
+    if nl.value == 0 and two_d:
+        # no level of >= 256 boxes runs the pair in the timed window: the
+        # split half-sweep on every level
+        kname = "k2_gsrb (half sweep, 16 B/cell)"
+        lib.call("profile_enable", case.tree.h, capi.PROF_GSRB)
+        for k in range(2):
+            unit_step(case, dt, args.warmup + args.steps + 2 + k)
+        case.tree.sync()
+        lib.call("profile_read", case.tree.h, C.byref(ms), C.byref(nl), C.byref(by))
+    if nl.value == 0 and two_d:
+        # no level of >= 256 boxes at all (config 1's set-up tree): the flux
+        # over every leaf (48 B/cell: the densities' two ghost layers read,
+        # the face fluxes written) is the line
+        kname = "k2_flux (all leaves, 48 B/cell)"
+        lib.call("profile_enable", case.tree.h, capi.PROF_FLUX)
+        for k in range(2):
+            unit_step(case, dt, args.warmup + args.steps + 4 + k)
+        case.tree.sync()
+        lib.call("profile_read", case.tree.h, C.byref(ms), C.byref(nl), C.byref(by))
+    if nl.value == 0 and not two_d:
+        # no level runs the fused pair (too few boxes per level, or
+        # electrode stencils): the split half-sweep k_gsrb is the smoother
+        kname = "k_gsrb (half-sweep, 16 B/cell)"
+        graphs = True
+        lib.call("profile_enable", case.tree.h, capi.PROF_GSRB)
+        for k in range(2):
+            unit_step(case, dt, args.warmup + args.steps + 2 + k)
+        case.tree.sync()
+        lib.call("profile_read", case.tree.h, C.byref(ms), C.byref(nl), C.byref(by))
+    # config 1: the level-1 solve (k2_cs_pfmg) per unit step over two eager
+    # steps, so that the line can also be read without it -- the reference's
+    # CPU timing cannot run it (HYPRE is absent)
+    cs_ms_step = None
+    if two_d:
+        lib.call("profile_enable", case.tree.h, capi.PROF_CS)
+        k0 = args.warmup + args.steps + 8
+        for k in range(2):
+            unit_step(case, dt, k0 + k)
+        case.tree.sync()
+        cms, cnl, cby = C.c_double(), C.c_int64(), C.c_double()
+        lib.call("profile_read", case.tree.h, C.byref(cms), C.byref(cnl), C.byref(cby))
+        lib.call("profile_enable", case.tree.h, 0)
+        cs_ms_step = cms.value / 2
+    # the fused species step (k_fe_lds, 64^3 boxes) over two eager unit steps
+    # after the timed region -- one Heun stage of each kind: when it takes
+    # more of a step than the smoother it is the dominant kernel of the line
+    fe = None
+    if not two_d and not sharded and CONFIGS[args.config][0] == 64:
+        lib.call("profile_enable", case.tree.h, capi.PROF_FE)
+        # the Heun sequence continued (after the smoother's two eager steps
+        # when V-cycle graphs ran): the rhs folded by the previous update
+        # stays valid, as in the timed region
+        k0 = args.warmup + args.steps + (2 if graphs else 0)
+        for k in range(2):
+            unit_step(case, dt, k0 + k)
+        case.tree.sync()
+        fms, fnl, fby = C.c_double(), C.c_int64(), C.c_double()
+        lib.call("profile_read", case.tree.h, C.byref(fms), C.byref(fnl), C.byref(fby))
+        lib.call("profile_enable", case.tree.h, 0)
+        if fnl.value:
+            fe = (fms.value, fnl.value, fby.value)
+    return ms, nl, by, kname, graphs, cs_ms_step, fe
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -511,7 +651,19 @@ def main():
                     help="level-1 solve: the reference's HYPRE PFMG restated "
                          "(AFH_COARSE_PFMG) or our exact separable solve "
                          "(AFH_COARSE_DIRECT); auto: PFMG on s3/s4/s5/2d")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: the dominant kernels' HBM-roofline "
+                         "lines (HIP events in or after the timed region, eager steps of "
+                         "their own), the 2-D level-1 solve's share and the CPU baseline "
+                         "(the C oracle on the same workload). Without it: set-up, warm-up, "
+                         "the timed steps and the result line only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last of them computed "
+                         "(species densities, potential, |E|; its residual and dt limits) "
+                         "as DIR/<name>.npy, float64; a seeded sample of the leaves' cells "
+                         "when they exceed 48 MB. One rank with the whole tree only")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full without the CPU baseline")
     ap.add_argument("--no-fused-rhs", action="store_true",
                     help="separate field_set_rhs pass instead of the rhs folded "
                          "into the density update (afh_fluid_set_rhs_output)")
@@ -618,12 +770,13 @@ def main():
         if dist is not None:
             dist.barrier()
 
-    # timed region: K steps. The dominant kernel (the fused red+black
+    if args.dump_outputs and (sharded or args.steps < 1):
+        raise SystemExit("--dump-outputs: one rank with the whole tree, at least one step")
+    # timed region: K steps. --full: the dominant kernel (the fused red+black
     # Gauss-Seidel pair on the leaf level) is timed with HIP events on the
     # tree's stream (afh_profile_*) over the same region -- unless V-cycles
     # are replayed as hipGraphs (kernel timing needs eager launches): then
     # over two eager unit steps right after the timed region
-    import ctypes as C
     graphs = args.graphs == "on" or (args.graphs == "auto" and args.config != "s1-64")
     if two_d:
         # the 2-D library replays its V-cycles as hipGraphs by itself
@@ -631,7 +784,7 @@ def main():
         # its kernels are timed after the timed region (launches of a few us
         # each, the events around them would weigh on the step clock)
         graphs = os.environ.get("AFH2_GRAPHS", "1") != "0"
-    elif not graphs:
+    elif not graphs and args.full:
         lib.call("profile_enable", case.tree.h, capi.PROF_GSRB_PAIR)
     barrier()
     case.tree.sync()
@@ -646,80 +799,13 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     ns1 = time.clock_gettime_ns(time.CLOCK_MONOTONIC)
-    if graphs or two_d:
-        lib.call("profile_enable", case.tree.h, capi.PROF_GSRB if two_d else capi.PROF_GSRB_PAIR)
-        for k in range(2):
-            unit_step(case, dt, args.warmup + args.steps + k)
-        case.tree.sync()
-    ms, nl, by = C.c_double(), C.c_int64(), C.c_double()
-    lib.call("profile_read", case.tree.h, C.byref(ms), C.byref(nl), C.byref(by))
-    kname = ("k_gsrb_pair2<%d,%d>" % (CONFIGS[args.config][0], CONFIGS[args.config][0])
-             if CONFIGS[args.config][0] > 16 else "k_gsrb_pair_box<%d>" % CONFIGS[args.config][0])
-    if two_d:
-        kname = ("k2_pair_box (red+black pair, levels of >= 256 boxes, 24 B/cell)"
-                 if os.environ.get("AFH_PAIR2D", "1") != "0" else
-                 "k2_gsrb (half sweep, levels of >= 256 boxes, 16 B/cell)")
-    if nl.value == 0 and two_d:
-        # no level of >= 256 boxes runs the pair in the timed window: the
-        # split half-sweep on every level
-        kname = "k2_gsrb (half sweep, 16 B/cell)"
-        lib.call("profile_enable", case.tree.h, capi.PROF_GSRB)
-        for k in range(2):
-            unit_step(case, dt, args.warmup + args.steps + 2 + k)
-        case.tree.sync()
-        lib.call("profile_read", case.tree.h, C.byref(ms), C.byref(nl), C.byref(by))
-    if nl.value == 0 and two_d:
-        # no level of >= 256 boxes at all (config 1's set-up tree): the flux
-        # over every leaf (48 B/cell: the densities' two ghost layers read,
-        # the face fluxes written) is the line
-        kname = "k2_flux (all leaves, 48 B/cell)"
-        lib.call("profile_enable", case.tree.h, capi.PROF_FLUX)
-        for k in range(2):
-            unit_step(case, dt, args.warmup + args.steps + 4 + k)
-        case.tree.sync()
-        lib.call("profile_read", case.tree.h, C.byref(ms), C.byref(nl), C.byref(by))
-    if nl.value == 0 and not two_d:
-        # no level runs the fused pair (too few boxes per level, or
-        # electrode stencils): the split half-sweep k_gsrb is the smoother
-        kname = "k_gsrb (half-sweep, 16 B/cell)"
-        graphs = True
-        lib.call("profile_enable", case.tree.h, capi.PROF_GSRB)
-        for k in range(2):
-            unit_step(case, dt, args.warmup + args.steps + 2 + k)
-        case.tree.sync()
-        lib.call("profile_read", case.tree.h, C.byref(ms), C.byref(nl), C.byref(by))
-    # config 1: the level-1 solve (k2_cs_pfmg) per unit step over two eager
-    # steps, so that the line can also be read without it -- the reference's
-    # CPU timing cannot run it (HYPRE is absent)
-    cs_ms_step = None
-    if two_d:
-        lib.call("profile_enable", case.tree.h, capi.PROF_CS)
-        k0 = args.warmup + args.steps + 8
-        for k in range(2):
-            unit_step(case, dt, k0 + k)
-        case.tree.sync()
-        cms, cnl, cby = C.c_double(), C.c_int64(), C.c_double()
-        lib.call("profile_read", case.tree.h, C.byref(cms), C.byref(cnl), C.byref(cby))
-        lib.call("profile_enable", case.tree.h, 0)
-        cs_ms_step = cms.value / 2
-    # the fused species step (k_fe_lds, 64^3 boxes) over two eager unit steps
-    # after the timed region -- one Heun stage of each kind: when it takes
-    # more of a step than the smoother it is the dominant kernel of the line
+    if args.dump_outputs and rank == 0:
+        # (the last timed step: a Heun stage 1 leaves state 1, a stage 2 state 0)
+        dump_outputs(case, (args.warmup + args.steps) % 2, last, args.dump_outputs)
     fe = None
-    if not two_d and not sharded and CONFIGS[args.config][0] == 64:
-        lib.call("profile_enable", case.tree.h, capi.PROF_FE)
-        # the Heun sequence continued (after the smoother's two eager steps
-        # when V-cycle graphs ran): the rhs folded by the previous update
-        # stays valid, as in the timed region
-        k0 = args.warmup + args.steps + (2 if graphs else 0)
-        for k in range(2):
-            unit_step(case, dt, k0 + k)
-        case.tree.sync()
-        fms, fnl, fby = C.c_double(), C.c_int64(), C.c_double()
-        lib.call("profile_read", case.tree.h, C.byref(fms), C.byref(fnl), C.byref(fby))
-        lib.call("profile_enable", case.tree.h, 0)
-        if fnl.value:
-            fe = (fms.value, fnl.value, fby.value)
+    if args.full:
+        ms, nl, by, kname, graphs, cs_ms_step, fe = kernel_lines(
+            args, lib, case, dt, graphs, two_d, sharded)
     if roctx:
         lib.call("profile_enable", case.tree.h, 0)
         k0 = args.warmup + args.steps + 6  # even: the window starts on a Heun stage 1
@@ -743,9 +829,6 @@ def main():
                        not args.no_fused_rhs and not two_d)
 
     if rank == 0:
-        avg_s = ms.value / 1e3 / max(1, nl.value)
-        bytes_per_launch = by.value / max(1, nl.value)
-        achieved = bytes_per_launch / avg_s / 1e9 if avg_s > 0 else 0.0
         out = {
             "metric": "cell-updates/s (fluid+MG V-cycle)",
             "value": ncell * args.steps * (1 if sharded else world) / elapsed,
@@ -769,16 +852,6 @@ def main():
                        "vcycle_graphs": graphs,
                        "parallelism": ("box-shard-%d-%s" % (world, args.shard)) if sharded else
                        ("replica-per-gpu" if world > 1 else "single-gpu")},
-            "roofline": {"bound": "hbm",
-                         "kernel": kname,
-                         "achieved": achieved, "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                         "traffic": pmc_traffic(args.config),
-                         "avg_launch_us": avg_s * 1e6,
-                         "algorithmic_bytes_per_launch": bytes_per_launch,
-                         "launches": nl.value,
-                         "timed_over": ("2 eager unit steps after the timed region"
-                                        if graphs or two_d else "the timed region")},
             "last_residual": last_res[-1] if last_res else None,
             # one FAS V(2,2)-cycle per step (SURVEY.md 8(d) reports both)
             "vcycles_per_s": args.steps / elapsed,
@@ -786,6 +859,20 @@ def main():
             # scripts/project_scaling.py)
             "window_ns": [ns0, ns1],
         }
+        if args.full:
+            avg_s = ms.value / 1e3 / max(1, nl.value)
+            bytes_per_launch = by.value / max(1, nl.value)
+            achieved = bytes_per_launch / avg_s / 1e9 if avg_s > 0 else 0.0
+            out["roofline"] = {"bound": "hbm",
+                               "kernel": kname,
+                               "achieved": achieved, "peak": HBM_PEAK_GBS,
+                               "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                               "traffic": pmc_traffic(args.config),
+                               "avg_launch_us": avg_s * 1e6,
+                               "algorithmic_bytes_per_launch": bytes_per_launch,
+                               "launches": nl.value,
+                               "timed_over": ("2 eager unit steps after the timed region"
+                                              if graphs or two_d else "the timed region")}
         if fe is not None:
             # the fused species step per unit step against the smoother's
             # (its launches over the timed region): the larger is the line
@@ -817,6 +904,7 @@ def main():
             out["config"]["ndim"] = 2
             out["config"]["fused_rhs"] = False
             out["config"]["chemistry"] = "air_chemistry_v1 (8 species, 25 reactions)"
+        if two_d and args.full:
             # the line without the level-1 solve, as the reference is timed
             ms_x = 1e3 * elapsed / args.steps - cs_ms_step
             out["level1_solve_ms_per_step"] = cs_ms_step
@@ -878,7 +966,7 @@ def main():
             out["config"]["gas_density"] = "variable (3d_sprite m_user: 2.5e25 exp(-z/7.2 km))"
             out["config"]["photoionization"] = ("Helmholtz Bourdon-3, every %d time steps"
                                                 % sim.c.i("photoi%per_steps"))
-        if not args.no_cpu_baseline and world == 1 and not two_d:
+        if args.full and not args.no_cpu_baseline and world == 1 and not two_d:
             out["cpu_baseline"] = (cpu_baseline_driver(sim, config=args.config)
                                    if args.config in DRIVER_CONFIGS else
                                    cpu_baseline(args.config, coarse))

@@ -10,7 +10,7 @@ for rep in $(seq ${REPS:-2}); do
     tag=${CFG:-s1-64}_${v//,/+}_$rep
     envs=()
     [ "$v" = default ] || IFS=',' read -ra envs <<< "$v"
-    env "${envs[@]}" timeout -k 10 400 python3 bench.py --config ${CFG:-s1-64} --steps ${STEPS:-10} \
+    env "${envs[@]}" timeout -k 10 400 python3 bench.py --full --config ${CFG:-s1-64} --steps ${STEPS:-10} \
       --warmup ${WARMUP:-2} --no-cpu-baseline > gpurun_out/envsets/$tag.log 2>&1 || { tail -3 gpurun_out/envsets/$tag.log; exit 1; }
     python3 -c "
 import json

@@ -6,7 +6,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out/rep
 CFG=${CFG:-s1-64}; N=${N:-3}
 for r in $(seq $N); do
-  timeout -k 10 300 python bench.py --config $CFG --steps ${STEPS:-20} --warmup ${WARMUP:-5} \
+  timeout -k 10 300 python bench.py --full --config $CFG --steps ${STEPS:-20} --warmup ${WARMUP:-5} \
     --no-cpu-baseline "$@" > gpurun_out/rep/${CFG}_$r.json 2> gpurun_out/rep/${CFG}_$r.err || exit $?
   python3 - gpurun_out/rep/${CFG}_$r.json <<'PY'
 import json, sys

@@ -9,7 +9,7 @@ for rep in $(seq ${REPS:-2}); do
   for v in $2; do
     tag=${CFG:-s1-64}_${VAR//,/+}_${v}_$rep
     for var in ${VAR//,/ }; do export "$var=$v"; done
-    timeout -k 10 400 python3 bench.py --config ${CFG:-s1-64} --steps ${STEPS:-10} --warmup 2 \
+    timeout -k 10 400 python3 bench.py --full --config ${CFG:-s1-64} --steps ${STEPS:-10} --warmup 2 \
       --no-cpu-baseline > gpurun_out/envbench/$tag.log 2>&1 || { tail -3 gpurun_out/envbench/$tag.log; exit 1; }
     python3 -c "
 import json, sys

@@ -12,7 +12,7 @@ export TMPDIR=/tmp
 CFGS=${CFGS:-"s3 s4 s5"}; GROW=${GROW:-4.33e6}; GS=${GS:-300}; K=${K:-20}
 mkdir -p gpurun_out
 for CFG in $CFGS; do
-  timeout -k 10 ${BTIME:-900} python3 -u bench.py --config $CFG --grow-cells $GROW \
+  timeout -k 10 ${BTIME:-900} python3 -u bench.py --full --config $CFG --grow-cells $GROW \
     --grow-seconds $GS --steps $K --warmup 3 > gpurun_out/grown_$CFG.json \
     2> gpurun_out/grown_$CFG.err
   rc=$?; echo "grown $CFG rc=$rc"; cut -c1-300 gpurun_out/grown_$CFG.json

@@ -9,7 +9,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
 CFG=${CFG:-s1-64}; K=${K:-5}
 mkdir -p gpurun_out/prof_$CFG
-timeout -k 10 ${BTIME:-600} python bench.py --config $CFG --steps ${BSTEPS:-10} --warmup 2 \
+timeout -k 10 ${BTIME:-600} python bench.py --full --config $CFG --steps ${BSTEPS:-10} --warmup 2 \
   ${BENCH_EXTRA:-} > gpurun_out/bench_$CFG.json 2> gpurun_out/bench_$CFG.err
 rc=$?; echo "bench $CFG rc=$rc"; cat gpurun_out/bench_$CFG.json | cut -c1-400
 [ $rc -eq 0 ] || { tail -5 gpurun_out/bench_$CFG.err; exit $rc; }
