@@ -106,12 +106,19 @@ class RefInfo:
         return len(self.rm)
 
 
+# af_t%coord_t (m_af_types.f90: af_xyz, af_cyl; the values of a .dat file and
+# of afh_tree_set_coord)
+AF_XYZ, AF_CYL = 1, 2
+
+
 class AfTree:
     """The af_t topology (m_af_types.f90:326-393) of a Cartesian tree, NDIM = 3
     (the default) or 2 (len(grid_size) == 2: afivo/lib_2d, BASELINE config 1)."""
 
     def __init__(self, n_cell, r_max, grid_size, periodic=None, r_min=None,
-                 box_limit=10 ** 7):
+                 box_limit=10 ** 7, coord=AF_XYZ):
+        """coord: AF_XYZ, or AF_CYL for an axisymmetric 2-D tree (first
+        coordinate r, second z; af_init's coord argument)."""
         nc = int(n_cell)
         if nc < 2 or nc % 2:
             raise ValueError("n_cell should be even and >= 2")
@@ -128,6 +135,11 @@ class AfTree:
         self.dr_base = (self.domain - self.r_base) / np.asarray(grid_size, float)
         self.coarse_grid_size = grid_size
         self.periodic = tuple(bool(p) for p in (periodic or (False,) * nd))
+        if coord not in (AF_XYZ, AF_CYL):
+            raise ValueError("coord %r" % (coord,))
+        if coord == AF_CYL and (nd != 2 or self.periodic[0] or self.r_base[0] < 0):
+            raise ValueError("cylindrical coordinates: 2-D, r not periodic, r_min >= 0")
+        self.coord = coord
         self.box_limit = int(box_limit)
         # per-box records, indexed by id (index 0 unused)
         self.lvl, self.ix, self.parent = [0], [None], [0]
@@ -435,9 +447,17 @@ class AfTree:
         return self.dr_base * 0.5 ** (lvl - 1)
 
     def total_volume(self):
-        """af_total_volume (m_af_utils.f90): the coarse boxes' volume (area
-        in 2-D)."""
+        """af_total_volume (m_af_types.f90:805-825): the coarse boxes' volume
+        (area in 2-D); in cylindrical coordinates the volume of their rings,
+        pi (r1^2 - r0^2) times the length in z."""
         v = 0.0
+        if self.coord == AF_CYL:
+            box_len = self.nc * self.dr_base
+            for bid in self.lvls[1]["ids"]:
+                r0 = float(self.r_min[bid][0])
+                r1 = r0 + float(box_len[0])
+                v = v + float(np.pi) * (r1 * r1 - r0 * r0) * float(box_len[-1])
+            return v
         for bid in self.lvls[1]["ids"]:
             v += float(np.prod(self.dr[bid] * self.nc))
         return v

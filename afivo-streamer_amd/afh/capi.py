@@ -211,6 +211,13 @@ SIGNATURES = {
     "dist_stats": (i32, [_VP, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "dist_peer_bytes": (i32, [_VP, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
 }
+# the entry points only the 2-D library has (include/afivo_hip_2d_cyl.h):
+# the tree's coordinate type, afivo's af_xyz / af_cyl
+SIGNATURES_2D = {
+    "tree_set_coord": (i32, [_VP, i32]),
+    "tree_get_coord": (i32, [_VP, P_i32]),
+}
+COORD_XYZ, COORD_CYL = 1, 2
 DIST_LOCAL, DIST_RCCL = 1, 2
 HOOK_HALO, HOOK_RIMS, HOOK_RESTRICT, HOOK_MAX, HOOK_MIN, HOOK_CFLUX = 1, 2, 3, 4, 5, 6
 HOOK_SUM = 7
@@ -240,18 +247,20 @@ class Library:
     """A loaded C-ABI library; call functions without their prefix."""
 
     def __init__(self, path, prefix, extra=None, only=None):
-        """only: the entry points the library implements (a subset of
-        SIGNATURES; the 2-D build's, include/afivo_hip_2d.h)."""
+        """only: the entry points of SIGNATURES the library implements (the
+        2-D build's subset, include/afivo_hip_2d.h). extra: entry points
+        outside SIGNATURES, bound as well."""
         if not os.path.exists(path):
             raise AfhError("shared library not built: %s" % path)
         self.path = path
         self.prefix = prefix
         self.lib = C.CDLL(path)
         sigs = dict(SIGNATURES)
-        if extra:
-            sigs.update(extra)
         if only is not None:
             sigs = {n: sigs[n] for n in only}
+        self.common = sorted(sigs)
+        if extra:
+            sigs.update(extra)
         self.fn = {}
         for name, (res, args) in sigs.items():
             f = getattr(self.lib, prefix + name)
@@ -267,7 +276,8 @@ class Library:
         return rc
 
     def symbols(self):
-        return [self.prefix + n for n in self.fn]
+        """The bound entry points of the common ABI (SIGNATURES)."""
+        return [self.prefix + n for n in self.common]
 
     def has(self, name):
         """Whether the library implements entry point `name` (the 2-D build
@@ -286,11 +296,11 @@ def hip_library():
 
 
 def hip_library_2d():
-    """The NDIM = 2 product library (the entry points of afivo_hip_2d.h).
-    Raises if it was not built -- no CPU fallback."""
+    """The NDIM = 2 product library (the entry points of afivo_hip_2d.h and
+    its own, SIGNATURES_2D). Raises if it was not built -- no CPU fallback."""
     if "hip2d" not in _loaded:
         only = [n[len("afh_"):] for n in header_symbols("afivo_hip_2d.h")]
-        _loaded["hip2d"] = Library(HIP_LIB_2D, "afh_", only=only)
+        _loaded["hip2d"] = Library(HIP_LIB_2D, "afh_", extra=SIGNATURES_2D, only=only)
     return _loaded["hip2d"]
 
 

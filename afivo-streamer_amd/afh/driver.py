@@ -30,7 +30,7 @@ import os
 import numpy as np
 
 from . import capi, electrode
-from .amr import AfTree
+from .amr import AF_CYL, AF_XYZ, AfTree
 from .model import Fluid, Multigrid, Tree, photoi_helmh_compute
 
 UC_EPS0 = 8.8541878176e-12
@@ -157,8 +157,21 @@ class Simulation:
         if c.s("time_integrator") != "heuns_method":
             raise NotImplementedError("time integrator %s" % c.s("time_integrator"))
         self.n_states = 2  # af_advance_num_steps(af_heuns_method)
-        if c.i("use_dielectric") or c.i("cylindrical"):
-            raise NotImplementedError("dielectric / cylindrical cases")
+        if c.i("use_dielectric"):
+            raise NotImplementedError("dielectric cases")
+        # cylindrical = T (streamer.f90:145-153: af_init with coord = af_cyl):
+        # the 2-D library's afh_tree_set_coord; its level-1 solve is PFMG
+        self.cylindrical = bool(c.i("cylindrical"))
+        if self.cylindrical:
+            if self.ndim != 2:
+                raise NotImplementedError("cylindrical coordinates need a 2-D case")
+            if not lib.has("tree_set_coord"):
+                raise NotImplementedError("cylindrical coordinates are built in the 2-D "
+                                          "library only (capi.hip_library_2d)")
+            if coarse_mode != capi.COARSE_PFMG:
+                raise ValueError("cylindrical coordinates: the exact level-1 solve does not "
+                                 "apply, pass coarse_mode=capi.COARSE_PFMG (with "
+                                 "coarse_cycles >= 1)")
         # electrode (m_field.f90:196-346): a rod or sphere as level-set
         # function; its operators are computed on the host per box
         # (afh.electrode, mg_set_operators_tree) and handed to the library
@@ -291,7 +304,7 @@ class Simulation:
         # mesh: af_init (streamer.f90:151-153)
         nc = c.i("box_size")
         self.af = AfTree(nc, self.origin + self.L, c.ia("coarse_grid_size_value"),
-                         r_min=self.origin)
+                         r_min=self.origin, coord=AF_CYL if self.cylindrical else AF_XYZ)
         self.tree = self.fluid = self.mg = None
         self.helm = []
         self.shard = None  # shard_over
@@ -425,6 +438,8 @@ class Simulation:
     def _create_tree(self):
         t = Tree(self.lib, self.af.topology(), self.n_var_tree, self.n_var_face,
                  device=self.device, box_capacity=self._capacity())
+        if self.cylindrical:
+            t.set_coord(capi.COORD_CYL)
         return self._set_methods(t)
 
     def _n_global(self):
@@ -918,6 +933,8 @@ class Simulation:
         info = self.af.adjust_refinement(fn)
         if info.n_add or info.n_rm:
             new = self.tree.regrid(self.af.topology())
+            if self.cylindrical:  # (inherited from the old tree; stated again)
+                new.set_coord(capi.COORD_CYL)
             old = self.tree
             self._bind(new)
             old.close()

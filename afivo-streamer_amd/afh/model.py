@@ -144,6 +144,20 @@ class Tree:
         return Tree(self.lib, topo, self.n_var_cell, self.n_var_face,
                     _regrid_of=self, box_capacity=self.box_capacity)
 
+    def set_coord(self, coord):
+        """The tree's coordinate type (capi.COORD_XYZ / COORD_CYL; the 2-D
+        library's afh_tree_set_coord): before any Multigrid or Fluid exists
+        on the tree. A regridded tree inherits it."""
+        self.lib.call("tree_set_coord", self.h, int(coord))
+
+    @property
+    def coord(self):
+        if not self.lib.has("tree_get_coord"):
+            return capi.COORD_XYZ
+        c = C.c_int32()
+        self.lib.call("tree_get_coord", self.h, C.byref(c))
+        return c.value
+
     def set_cc_prolong(self, iv, method, limiter=None):
         """tree%cc_methods(iv)%prolong (capi.PROLONG_LINEAR / PROLONG_LIMIT)
         and prolong_limiter; iv becomes an automatic variable. The default

@@ -39,6 +39,15 @@
 //   k2_consistent af_consistent_fluxes / flux_from_children (m_af_core.f90:1257-1357)
 //   k2_update     flux_update_densities (m_af_flux_schemes.f90:320-394) +
 //                 add_source_terms / get_rates / get_derivatives (field forms)
+//
+// Cylindrical coordinates (af_cyl, afh_tree_set_coord): k2_gsrb_cyl,
+// k2_pair_box_cyl, k2_residual_cyl, k2_rstr_fas_cyl, k2_parent_rhs_cyl (the
+// stencil with cylindrical_gradient, m_af_stencil.f90:381-404, 863-889),
+// k2_restrict_cyl (af_restrict_box with af_cyl_child_weights,
+// m_af_restrict.f90:93-106), k2_consistent_cyl (m_af_core.f90:1338-1351),
+// k2_update_cyl (m_af_flux_schemes.f90:395-406), k2_box_sum_cyl (sum_2pr_box,
+// m_af_utils.f90:1008-1024) and the per-cell PFMG level-1 coefficients. They
+// are separate kernels: a Cartesian tree launches exactly what it did before.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdarg.h>
@@ -296,6 +305,86 @@ struct Coef2 {
   double inv_c1;
 };
 
+// ---- cylindrical coordinates (af_cyl: first index r, second z). The
+// Cartesian kernels keep their code and arguments; a cylindrical tree
+// launches the *_cyl kernels below instead.
+//
+// The Laplacian stays the constant stencil with cylindrical_gradient set
+// (m_af_multigrid.f90:1227-1243): per first index i the entries are
+// (m_af_stencil.f90:389-395, 872-878, af_cyl_flux_factors m_af_types.f90:
+// 1199-1211)
+//   r = r_min + (i - 0.5) dr, inv_r = 1 / r,
+//   c2 = ((r - 0.5 dr) inv_r) c(2), c3 = ((r + 0.5 dr) inv_r) c(3),
+//   c1 = c(1) - (c2 - c(2)) - (c3 - c(3)), inv = 1 / c1
+// formed once per box into a table q[0..3] = (c1, c2, c3, inv) per i; c(4:)
+// are the level's. On the axis (r_min = 0, i = 1) the inner factor is exactly
+// 0 and so is c2: nothing divides by either.
+__host__ __device__ __forceinline__ void cyl_flux_factors(double r_min, double dr, int i,
+                                                          double &f1, double &f2) {
+  const double r = r_min + (i - 0.5) * dr;
+  const double inv_r = 1 / r;
+  f1 = (r - 0.5 * dr) * inv_r;
+  f2 = (r + 0.5 * dr) * inv_r;
+}
+
+__host__ __device__ __forceinline__ void cyl_coef(const Coef2 &cf, double r_min, double dr,
+                                                  int i, double *q) {
+  double f1, f2;
+  cyl_flux_factors(r_min, dr, i, f1, f2);
+  q[1] = f1 * cf.c[1];
+  q[2] = f2 * cf.c[2];
+  q[0] = cf.c[0] - (q[1] - cf.c[1]) - (q[2] - cf.c[2]);
+  q[3] = 1 / q[0];
+}
+
+// af_cyl_child_weights of coarse cell i (m_af_types.f90:1187-1196)
+__host__ __device__ __forceinline__ void cyl_child_weights(double r_min, double dr, int i,
+                                                           double &inner, double &outer) {
+  const double tmp = 0.25 * dr / (r_min + (i - 0.5) * dr);
+  inner = 1 - tmp;
+  outer = 1 + tmp;
+}
+
+// the table of box m into T[4 nc] (LDS), by the whole workgroup
+__device__ __forceinline__ void cyl_table(double *T, const Coef2 &cf, const afh_box_meta &m,
+                                          int nc) {
+  for (int i = threadIdx.x; i < nc; i += blockDim.x)
+    cyl_coef(cf, m.r_min[0], m.dr[0], i + 1, T + 4 * i);
+  __syncthreads();
+}
+
+// stencil_apply_357's cylindrical branch: q the table entry of the cell's i
+__device__ __forceinline__ double apply5_cyl(const double *p, int x, int ng, const double *q,
+                                             const Coef2 &cf) {
+  return q[0] * p[x] + q[1] * p[x - 1] + q[2] * p[x + 1] + cf.c[3] * p[x - ng] +
+         cf.c[4] * p[x + ng];
+}
+
+// stencil_gsrb_357, cylindrical_gradient (m_af_stencil.f90:863-889); 4 nc
+// doubles of dynamic LDS
+__global__ void __launch_bounds__(NT)
+    k2_gsrb_cyl(double *__restrict__ phi, const double *__restrict__ rhs,
+                const afh_box_meta *__restrict__ meta, const int32_t *__restrict__ ids, int nc,
+                int bsz, Coef2 cf, int redblack) {
+  extern __shared__ double cyl_T[];
+  const int id = ids[blockIdx.y];
+  cyl_table(cyl_T, cf, meta[id - 1], nc);
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  const int half = nc >> 1;
+  if (t >= nc * half) return;
+  const int j = t / half + 1, q = t % half;
+  const int i0 = 2 - ((redblack ^ j) & 1);
+  const int i = i0 + 2 * q;
+  const int ng = nc + 2;
+  const size_t o = (size_t)(id - 1) * bsz;
+  double *p = phi + o;
+  const int x = ix2(ng, i, j);
+  const double *c = cyl_T + 4 * (i - 1);
+  p[x] = (rhs[o + x] - c[1] * p[x - 1] - c[2] * p[x + 1] - cf.c[3] * p[x - ng] -
+          cf.c[4] * p[x + ng]) *
+         c[3];
+}
+
 __global__ void __launch_bounds__(NT)
     k2_gsrb(double *__restrict__ phi, const double *__restrict__ rhs,
             const int32_t *__restrict__ ids, int nc, int bsz, Coef2 cf, int redblack) {
@@ -473,6 +562,158 @@ __global__ void __launch_bounds__(64)
   }
 }
 
+// The pair once more for a cylindrical tree (k2_pair_box_cyl; CYL = true is
+// the only instantiation -- the Cartesian kernel above keeps its own text, so
+// that its code is what it was). Its table T holds the
+// box's own entries 0 .. NC-1 and, for phase B across an r-face, the
+// same-level neighbour's boundary cell built from the neighbour's own r_min
+// and index (entry NC: the low neighbour's cell NC, NC+1: the high
+// neighbour's cell 1; this box's r_min -+ NC dr can differ in the last bit).
+// A z-neighbour of the same level has this box's radii.
+template <int NC, int LPB, bool CYL>
+__device__ __forceinline__ void
+pair_box_body(const double *__restrict__ src, double *__restrict__ dst,
+              const double *__restrict__ rhs, const double *__restrict__ coarse,
+              const afh_box_meta *__restrict__ meta, const int32_t *__restrict__ ids, int n,
+              int bsz, Coef2 cf, Bc4 g) {
+  constexpr int NG = NC + 2, NB = NG * NG, NT = LPB, H = NC / 2, PW = 64 / LPB;
+  __shared__ double P_[PW][NB];
+  __shared__ double T_[CYL ? PW : 1][CYL ? 4 * (NC + 2) : 1];
+  const int sub = threadIdx.x / LPB, tid = threadIdx.x % LPB;
+  const int bidx = blockIdx.x * PW + sub;
+  const bool valid = bidx < n;
+  double *P = P_[sub];
+  const double *T = T_[CYL ? sub : 0];
+  const int id = ids[valid ? bidx : n - 1];
+  const afh_box_meta &m = meta[id - 1];
+  if (CYL) {
+    static_assert(!CYL || NC + 2 <= LPB, "one lane per table entry");
+    double *Tw = T_[CYL ? sub : 0];
+    if (tid < NC) {
+      cyl_coef(cf, m.r_min[0], m.dr[0], tid + 1, Tw + 4 * tid);
+    } else if (tid < NC + 2) {
+      const int nid = m.neighbors[tid - NC];
+      if (nid > 0)
+        cyl_coef(cf, meta[nid - 1].r_min[0], meta[nid - 1].dr[0], tid == NC ? NC : 1,
+                 Tw + 4 * tid);
+    }
+  }
+  const double *x = src + (size_t)(id - 1) * bsz, *r = rhs + (size_t)(id - 1) * bsz;
+  double *y = dst + (size_t)(id - 1) * bsz;
+  for (int e = tid; e < NB; e += NT) P[e] = x[e];
+  // B inputs: the odd ghost u < 2 NC (face u / H + 1, its odd positions) of
+  // a same-level neighbour -- the neighbour's boundary cell, its four
+  // neighbours and rhs, loaded before A
+  constexpr int NGH = 2 * NC, GPT = (NGH + NT - 1) / NT;
+  double bl[GPT][5];
+  for (int q = 0; q < GPT; q++) {
+    const int u = tid + NT * q;
+    for (int k = 0; k < 5; k++) bl[q][k] = 0.0;
+    if (u >= NGH) continue;
+    const int nb = u / H + 1, d = (nb - 1) >> 1;
+    const bool low = ((nb - 1) & 1) == 0;
+    const int gi = low ? 0 : NC + 1;
+    const int a = 2 * (u % H) + 1 + ((gi & 1) ? 1 : 0);  // gi + a odd
+    const int nid = m.neighbors[nb - 1];
+    if (nid > 0) {
+      auto at = [&](int n, int tg) { return d == 0 ? ix2(NG, n, tg) : ix2(NG, tg, n); };
+      const double *xs = src + (size_t)(nid - 1) * bsz;
+      const int c = at(low ? NC : 1, a);
+      bl[q][0] = xs[c - 1];
+      bl[q][1] = xs[c + 1];
+      bl[q][2] = xs[c - NG];
+      bl[q][3] = xs[c + NG];
+      bl[q][4] = rhs[(size_t)(nid - 1) * bsz + c];
+    }
+  }
+  __syncthreads();
+  // A: odd cells (k2_gsrb with an odd red-black counter)
+  for (int q = tid; q < NC * H; q += NT) {
+    const int j = q / H + 1, i = 2 - ((1 ^ j) & 1) + 2 * (q % H);
+    const int c = ix2(NG, i, j);
+    if (CYL) {
+      const double *tc = T + 4 * (i - 1);
+      P[c] = (r[c] - tc[1] * P[c - 1] - tc[2] * P[c + 1] - cf.c[3] * P[c - NG] -
+              cf.c[4] * P[c + NG]) *
+             tc[3];
+    } else {
+      P[c] = (r[c] - cf.c[1] * P[c - 1] - cf.c[2] * P[c + 1] - cf.c[3] * P[c - NG] -
+              cf.c[4] * P[c + NG]) *
+             cf.inv_c1;
+    }
+  }
+  __syncthreads();
+  // B: odd face ghosts
+  for (int q = 0; q < GPT; q++) {
+    const int u = tid + NT * q;
+    if (u >= NGH) continue;
+    const int nb = u / H + 1, d = (nb - 1) >> 1;
+    const bool low = ((nb - 1) & 1) == 0;
+    const int gi = low ? 0 : NC + 1, i1 = low ? 1 : NC, i2 = low ? 2 : NC - 1;
+    const int a = 2 * (u % H) + 1 + ((gi & 1) ? 1 : 0);
+    auto at = [&](int n, int tg) { return d == 0 ? ix2(NG, n, tg) : ix2(NG, tg, n); };
+    const int nid = m.neighbors[nb - 1];
+    double v;
+    if (nid > 0 && CYL) {
+      // the neighbour's boundary cell: its own entry across an r-face
+      const double *tc = T + 4 * (d == 0 ? (low ? NC : NC + 1) : a - 1);
+      v = (bl[q][4] - tc[1] * bl[q][0] - tc[2] * bl[q][1] - cf.c[3] * bl[q][2] -
+           cf.c[4] * bl[q][3]) *
+          tc[3];
+    } else if (nid > 0)
+      v = (bl[q][4] - cf.c[1] * bl[q][0] - cf.c[2] * bl[q][1] - cf.c[3] * bl[q][2] -
+           cf.c[4] * bl[q][3]) *
+          cf.inv_c1;
+    else
+      v = gc2_face(coarse, meta, m, nb, nid, a, P[at(i1, a)], P[at(i2, a)], NC, bsz, g);
+    P[at(gi, a)] = v;
+  }
+  __syncthreads();
+  // C: even cells
+  for (int q = tid; q < NC * H; q += NT) {
+    const int j = q / H + 1, i = 2 - ((0 ^ j) & 1) + 2 * (q % H);
+    const int c = ix2(NG, i, j);
+    if (CYL) {
+      const double *tc = T + 4 * (i - 1);
+      P[c] = (r[c] - tc[1] * P[c - 1] - tc[2] * P[c + 1] - cf.c[3] * P[c - NG] -
+              cf.c[4] * P[c + NG]) *
+             tc[3];
+    } else {
+      P[c] = (r[c] - cf.c[1] * P[c - 1] - cf.c[2] * P[c + 1] - cf.c[3] * P[c - NG] -
+              cf.c[4] * P[c + NG]) *
+             cf.inv_c1;
+    }
+  }
+  __syncthreads();
+  // store: interior and corners; the four faces' ghosts pushed
+  for (int e = tid; e < NB; e += NT) {
+    const int i = e % NG, j = e / NG;
+    const int nout = (i == 0 || i == NG - 1) + (j == 0 || j == NG - 1);
+    if (valid && nout != 1) y[e] = P[e];
+  }
+  for (int u = valid ? tid : 4 * NC; u < 4 * NC; u += NT) {
+    const int nb = u / NC + 1, a = u % NC + 1, d = (nb - 1) >> 1;
+    const bool low = ((nb - 1) & 1) == 0;
+    const int gi = low ? 0 : NC + 1, i1 = low ? 1 : NC, i2 = low ? 2 : NC - 1;
+    auto at = [&](int n, int tg) { return d == 0 ? ix2(NG, n, tg) : ix2(NG, tg, n); };
+    const int nid = m.neighbors[nb - 1];
+    if (nid > 0)
+      dst[(size_t)(nid - 1) * bsz + at(low ? NC + 1 : 0, a)] = P[at(i1, a)];
+    else
+      y[at(gi, a)] = gc2_face(coarse, meta, m, nb, nid, a, P[at(i1, a)], P[at(i2, a)], NC,
+                              bsz, g);
+  }
+}
+
+template <int NC, int LPB = 64>
+__global__ void __launch_bounds__(64)
+    k2_pair_box_cyl(const double *__restrict__ src, double *__restrict__ dst,
+                    const double *__restrict__ rhs, const double *__restrict__ coarse,
+                    const afh_box_meta *__restrict__ meta, const int32_t *__restrict__ ids,
+                    int n, int bsz, Coef2 cf, Bc4 g) {
+  pair_box_body<NC, LPB, true>(src, dst, rhs, coarse, meta, ids, n, bsz, cf, g);
+}
+
 __device__ __forceinline__ double apply5(const double *p, int x, int ng, const Coef2 &cf) {
   return cf.c[0] * p[x] + cf.c[1] * p[x - 1] + cf.c[2] * p[x + 1] + cf.c[3] * p[x - ng] +
          cf.c[4] * p[x + ng];
@@ -557,6 +798,104 @@ __global__ void __launch_bounds__(NT)
   const int i = t % ng, j = t / ng;
   double r = rhs[o + t];
   if (i >= 1 && i <= nc && j >= 1 && j <= nc) r = apply5(phi + o, t, ng, cf);
+  rhs[o + t] = r + tmp[o + t];
+  if (copy) tmp[o + t] = phi[o + t];
+}
+
+// ---- the cylindrical forms of the four kernels above (4 nc doubles of
+// dynamic LDS each: the box's coefficient table, or its parent's child
+// weights)
+__global__ void __launch_bounds__(NT)
+    k2_residual_cyl(const double *__restrict__ phi, const double *__restrict__ rhs,
+                    double *__restrict__ tmp, const int32_t *__restrict__ ids, int nc, int bsz,
+                    Coef2 cf, unsigned long long *red, const Coef2 *__restrict__ lvl_c,
+                    const afh_box_meta *__restrict__ meta) {
+  extern __shared__ double cyl_T[];
+  const int id = ids[blockIdx.y];
+  const afh_box_meta &m = meta[id - 1];
+  const Coef2 c = lvl_c ? lvl_c[m.lvl - 1] : cf;
+  cyl_table(cyl_T, c, m, nc);
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  double mx = 0.0;
+  if (t < nc * nc) {
+    const int i = t % nc + 1, j = t / nc + 1, ng = nc + 2;
+    const size_t o = (size_t)(id - 1) * bsz;
+    const int x = ix2(ng, i, j);
+    const double r = rhs[o + x] - apply5_cyl(phi + o, x, ng, cyl_T + 4 * (i - 1), c);
+    tmp[o + x] = r;
+    mx = fabs(r);
+  }
+  if (red) block_fold<true>(mx, red);
+}
+
+// update_coarse per child in af_cyl: the residual restricted with the
+// parent's child weights (af_restrict_box with geometry, m_af_restrict.f90:
+// 93-106: 0.25 (w1 sum(cc(i_f, j_f:j_f+1)) + w2 sum(cc(i_f+1, j_f:j_f+1)))),
+// phi without (mg_box_rstr_lpl, m_af_multigrid.f90:1215-1222)
+__global__ void __launch_bounds__(NT)
+    k2_rstr_fas_cyl(double *__restrict__ phi, const double *__restrict__ rhs,
+                    double *__restrict__ tmp, const afh_box_meta *__restrict__ meta,
+                    const int32_t *__restrict__ ids, int nc, int bsz, Coef2 cf) {
+  extern __shared__ double cyl_T[];
+  const int id = ids[blockIdx.y];
+  const afh_box_meta &m = meta[id - 1];
+  cyl_table(cyl_T, cf, m, nc);
+  const int hnc = nc >> 1;
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= hnc * hnc) return;
+  const int ii = t % hnc + 1, jj = t / hnc + 1, ng = nc + 2;
+  const int ic = ((m.ix[0] - 1) & 1) * hnc + ii, jc = ((m.ix[1] - 1) & 1) * hnc + jj;
+  const int i_f = 2 * ii - 1, j_f = 2 * jj - 1;
+  const size_t o = (size_t)(id - 1) * bsz, po = (size_t)(m.parent - 1) * bsz;
+  const double *p = phi + o, *r = rhs + o;
+  const int x00 = ix2(ng, i_f, j_f), x10 = x00 + 1, x01 = x00 + ng, x11 = x01 + 1;
+  const double *q0 = cyl_T + 4 * (i_f - 1), *q1 = q0 + 4;
+  const double r00 = r[x00] - apply5_cyl(p, x00, ng, q0, cf),
+               r10 = r[x10] - apply5_cyl(p, x10, ng, q1, cf),
+               r01 = r[x01] - apply5_cyl(p, x01, ng, q0, cf),
+               r11 = r[x11] - apply5_cyl(p, x11, ng, q1, cf);
+  const afh_box_meta &mp = meta[m.parent - 1];
+  double w1, w2;
+  cyl_child_weights(mp.r_min[0], mp.dr[0], ic, w1, w2);
+  tmp[po + ix2(ng, ic, jc)] = 0.25 * (w1 * (r00 + r01) + w2 * (r10 + r11));
+  phi[po + ix2(ng, ic, jc)] = 0.25 * (p[x00] + p[x10] + p[x01] + p[x11]);
+}
+
+// af_restrict_box with geometry in af_cyl
+__global__ void __launch_bounds__(NT)
+    k2_restrict_cyl(double *__restrict__ v, const afh_box_meta *__restrict__ meta,
+                    const int32_t *__restrict__ ids, int nc, int bsz) {
+  const int hnc = nc >> 1;
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= hnc * hnc) return;
+  const int id = ids[blockIdx.y];
+  const afh_box_meta &m = meta[id - 1];
+  const int ii = t % hnc + 1, jj = t / hnc + 1, ng = nc + 2;
+  const int ic = ((m.ix[0] - 1) & 1) * hnc + ii, jc = ((m.ix[1] - 1) & 1) * hnc + jj;
+  const double *c = v + (size_t)(id - 1) * bsz;
+  const int x00 = ix2(ng, 2 * ii - 1, 2 * jj - 1);
+  const afh_box_meta &mp = meta[m.parent - 1];
+  double w1, w2;
+  cyl_child_weights(mp.r_min[0], mp.dr[0], ic, w1, w2);
+  v[(size_t)(m.parent - 1) * bsz + ix2(ng, ic, jc)] =
+      0.25 * (w1 * (c[x00] + c[x00 + ng]) + w2 * (c[x00 + 1] + c[x00 + ng + 1]));
+}
+
+__global__ void __launch_bounds__(NT)
+    k2_parent_rhs_cyl(const double *__restrict__ phi, double *__restrict__ rhs,
+                      double *__restrict__ tmp, const afh_box_meta *__restrict__ meta,
+                      const int32_t *__restrict__ ids, int nc, int bsz, Coef2 cf, int copy) {
+  extern __shared__ double cyl_T[];
+  const int id = ids[blockIdx.y];
+  cyl_table(cyl_T, cf, meta[id - 1], nc);
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  const int ng = nc + 2;
+  if (t >= ng * ng) return;
+  const size_t o = (size_t)(id - 1) * bsz;
+  const int i = t % ng, j = t / ng;
+  double r = rhs[o + t];
+  if (i >= 1 && i <= nc && j >= 1 && j <= nc)
+    r = apply5_cyl(phi + o, t, ng, cyl_T + 4 * (i - 1), cf);
   rhs[o + t] = r + tmp[o + t];
   if (copy) tmp[o + t] = phi[o + t];
 }
@@ -961,8 +1300,14 @@ __global__ void __launch_bounds__(NT)
 
 // flux_from_children: the face fluxes of a leaf next to refined boxes are
 // the mean of the two fine faces; task = (parent id << 3) | nb
-__global__ void k2_consistent(double *__restrict__ F, const afh_box_meta *__restrict__ meta,
-                              const int32_t *__restrict__ tasks, int ntask, int nc, int fsz) {
+// CYL (k2_consistent_cyl): on faces normal to z the two fine fluxes are
+// weighted with the coarse neighbour's child weights (m_af_core.f90:1338-1351);
+// faces normal to r stay the plain mean
+template <bool CYL>
+__device__ __forceinline__ void consistent_body(double *__restrict__ F,
+                                                const afh_box_meta *__restrict__ meta,
+                                                const int32_t *__restrict__ tasks, int ntask,
+                                                int nc, int fsz) {
   const int nch = nc >> 1;
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= ntask * 2 * nch) return;
@@ -988,9 +1333,28 @@ __global__ void k2_consistent(double *__restrict__ F, const afh_box_meta *__rest
         0.5 * (fc[(2 * n - 2) * nf + (i - 1)] + fc[(2 * n - 1) * nf + (i - 1)]);
   } else {
     const int in = nch * cdix[i_ch - 1][0] + n;
-    fn[(i_nb - 1) * nf + (in - 1)] =
-        0.5 * (fc[(i - 1) * nf + (2 * n - 2)] + fc[(i - 1) * nf + (2 * n - 1)]);
+    if (CYL) {
+      const afh_box_meta &mn = meta[nb_id - 1];
+      double w1, w2;
+      cyl_child_weights(mn.r_min[0], mn.dr[0], in, w1, w2);
+      fn[(i_nb - 1) * nf + (in - 1)] =
+          0.5 * (w1 * fc[(i - 1) * nf + (2 * n - 2)] + w2 * fc[(i - 1) * nf + (2 * n - 1)]);
+    } else {
+      fn[(i_nb - 1) * nf + (in - 1)] =
+          0.5 * (fc[(i - 1) * nf + (2 * n - 2)] + fc[(i - 1) * nf + (2 * n - 1)]);
+    }
   }
+}
+
+__global__ void k2_consistent(double *__restrict__ F, const afh_box_meta *__restrict__ meta,
+                              const int32_t *__restrict__ tasks, int ntask, int nc, int fsz) {
+  consistent_body<false>(F, meta, tasks, ntask, nc, fsz);
+}
+
+__global__ void k2_consistent_cyl(double *__restrict__ F, const afh_box_meta *__restrict__ meta,
+                                  const int32_t *__restrict__ tasks, int ntask, int nc,
+                                  int fsz) {
+  consistent_body<true>(F, meta, tasks, ntask, nc, fsz);
 }
 
 struct DevReaction {
@@ -1098,6 +1462,86 @@ __global__ void __launch_bounds__(NT)
   if (A.last_step) block_fold<false>(cmin, red);
 }
 
+// The update once more for a cylindrical tree (k2_update_cyl, CYL = true the
+// only instantiation; k2_update above keeps its own text): the r-fluxes times
+// af_cyl_flux_factors inside the divergence (m_af_flux_schemes.f90:395-406)
+template <int NS, bool CYL>
+__device__ __forceinline__ void
+update_body(UpdArgs A, const int32_t *__restrict__ ids,
+            const afh_box_meta *__restrict__ meta, int nc, int bsz, int fsz,
+            unsigned long long *red) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  double cmin = 1e100;
+  const int ns = NS == MAXS ? A.ns : NS;
+  if (t < nc * nc) {
+    const int id = ids[blockIdx.y];
+    const int i = t % nc + 1, j = t / nc + 1, ng = nc + 2, nf = nc + 1;
+    const size_t x = (size_t)(id - 1) * bsz + ix2(ng, i, j);
+    double y[NS], dens[NS], der[NS];
+#pragma unroll
+    for (int s = 0; s < ns; s++) {
+      double tmp = 0.0;
+      for (int q = 0; q < A.n_prev; q++) tmp = tmp + A.w_prev[q] * A.prev[s][q][x];
+      y[s] = tmp;
+      const double v = A.der[s][x];
+      dens[s] = v > 0.0 ? v : 0.0;
+      der[s] = 0.0;
+    }
+    const double field = 1e21 * A.inv_N * A.E[x];
+    for (int r = 0; r < A.nr; r++) {
+      const DevReaction &R = A.reac[r];
+      double rate = rate_of(A, R, field);
+      double prod = 1.0;
+      for (int q = 0; q < R.n_in; q++) prod = prod * dens[R.ix_in[q] - 1];
+      rate = rate * prod;
+      for (int q = 0; q < R.n_in; q++) der[R.ix_in[q] - 1] = der[R.ix_in[q] - 1] - rate;
+      for (int q = 0; q < R.n_out; q++)
+        der[R.ix_out[q] - 1] = der[R.ix_out[q] - 1] + rate * R.mult_out[q];
+    }
+    if (A.last_step) {
+      const double eps = 1e-100;
+#pragma unroll
+      for (int s = 0; s < ns; s++) {
+        double a, b;
+        if (A.dt_chemistry_nmin > 0) {
+          a = dens[s] + A.dt_chemistry_nmin;
+          b = fabs(der[s]);
+          b = b > eps ? b : eps;
+        } else {
+          a = dens[s] > eps ? dens[s] : eps;
+          b = -der[s] > eps ? -der[s] : eps;
+        }
+        cmin = fmin(cmin, a / b);
+      }
+    }
+#pragma unroll
+    for (int s = 0; s < ns; s++) y[s] = y[s] + A.dt * der[s];
+    const double *F = A.F + (size_t)(id - 1) * fsz;
+    const int f0 = (j - 1) * nf + (i - 1), d2 = nf * nf;
+    const double dtx = A.dt / meta[id - 1].dr[0], dty = A.dt / meta[id - 1].dr[1];
+    const int e = A.e_index;
+    if (CYL) {
+      double rf1, rf2;
+      cyl_flux_factors(meta[id - 1].r_min[0], meta[id - 1].dr[0], i, rf1, rf2);
+      y[e] = y[e] + dtx * (rf1 * F[f0] - rf2 * F[f0 + 1]) +
+             dty * (F[d2 + f0] - F[d2 + f0 + nf]);
+    } else {
+      y[e] = y[e] + dtx * (F[f0] - F[f0 + 1]) + dty * (F[d2 + f0] - F[d2 + f0 + nf]);
+    }
+#pragma unroll
+    for (int s = 0; s < ns; s++) A.out[s][x] = y[s];
+  }
+  if (A.last_step) block_fold<false>(cmin, red);
+}
+
+template <int NS>
+__global__ void __launch_bounds__(NT)
+    k2_update_cyl(UpdArgs A, const int32_t *__restrict__ ids,
+                  const afh_box_meta *__restrict__ meta, int nc, int bsz, int fsz,
+                  unsigned long long *red) {
+  update_body<NS, true>(A, ids, meta, nc, bsz, fsz, red);
+}
+
 __global__ void k2_red_fill(unsigned long long *red, unsigned long long v) {
   red[threadIdx.x + blockIdx.x * blockDim.x] = v;
 }
@@ -1160,6 +1604,13 @@ struct afh_tree {
   int nc = 0, ng = 0, nb = 0, nlvl = 0, nvc = 0, nvf = 0;
   int bsz = 0, fsz = 0;
   int cgs[2] = {0, 0};
+  // afh_tree_set_coord: AFH_COORD_XYZ / AFH_COORD_CYL (af_xyz / af_cyl); fixed
+  // once a multigrid or fluid object exists on the tree
+  int coord = AFH_COORD_XYZ;
+  bool coord_fixed = false;
+  int periodic0 = 0;
+  double r_base0 = 0.0;
+  bool cyl() const { return coord == AFH_COORD_CYL; }
   std::vector<afh_box_meta> boxes;
   afh_box_meta *d_boxes = nullptr;
   LevelList ids, leaves, parents, refb, children_of, cflux;
@@ -1337,10 +1788,48 @@ static int32_t check_iv(afh_tree *t, int iv, const char *what) {
   return AFH_OK;
 }
 
+// af_restrict_box of the boxes ids (children -> parents): with the child
+// weights on a cylindrical tree unless geometry is false (phi of the
+// multigrid, mg_box_rstr_lpl)
+static void restrict_boxes(afh_tree *t, double *v, const int32_t *ids, int n, bool geometry) {
+  const int w = t->nc * t->nc / 4;
+  if (t->cyl() && geometry)
+    hipLaunchKernelGGL(k2_restrict_cyl, grid2(w, n), blk2(w), 0, t->stream, v, t->d_boxes, ids,
+                       t->nc, t->bsz);
+  else
+    hipLaunchKernelGGL(k2_restrict, grid2(w, n), blk2(w), 0, t->stream, v, t->d_boxes, ids,
+                       t->nc, t->bsz);
+}
+
+// dynamic LDS of the *_cyl kernels' coefficient table
+static inline size_t cyl_lds(const afh_tree *t) { return sizeof(double) * 4 * t->nc; }
+
 }  // namespace afh2
 
 // ============================================================ C ABI
 extern "C" {
+
+int32_t afh_tree_set_coord(afh_tree *t, int32_t coord) {
+  if (!t) return set_error(AFH_ERR_ARG, "afh_tree_set_coord: null tree");
+  if (coord != AFH_COORD_XYZ && coord != AFH_COORD_CYL)
+    return set_error(AFH_ERR_ARG, "afh_tree_set_coord: coordinate type %d", coord);
+  if (t->coord_fixed)
+    return set_error(AFH_ERR_STATE,
+                     "afh_tree_set_coord: after afh_mg_create / afh_fluid_create on the tree");
+  if (coord == AFH_COORD_CYL && t->periodic0)
+    return set_error(AFH_ERR_ARG, "afh_tree_set_coord: cylindrical with a periodic r");
+  if (coord == AFH_COORD_CYL && t->r_base0 < 0)
+    return set_error(AFH_ERR_ARG, "afh_tree_set_coord: cylindrical with r_base[0] = %g < 0",
+                     t->r_base0);
+  t->coord = coord;
+  return AFH_OK;
+}
+
+int32_t afh_tree_get_coord(afh_tree *t, int32_t *coord) {
+  if (!t || !coord) return set_error(AFH_ERR_ARG, "afh_tree_get_coord: null");
+  *coord = t->coord;
+  return AFH_OK;
+}
 
 const char *afh_last_error(void) { return afh2::g_err.c_str(); }
 
@@ -1361,6 +1850,7 @@ int32_t afh_tree_create(const afh_tree_desc *desc, int32_t device, afh_tree **ou
   t->nvc = desc->n_var_cell, t->nvf = desc->n_var_face;
   t->bsz = t->ng * t->ng, t->fsz = 2 * (nc + 1) * (nc + 1);
   t->cgs[0] = desc->coarse_grid_size[0], t->cgs[1] = desc->coarse_grid_size[1];
+  t->periodic0 = desc->periodic[0], t->r_base0 = desc->r_base[0];
   t->boxes.assign(desc->boxes, desc->boxes + t->nb);
   t->meth.assign(t->nvc + 1, Meth());
   auto lists = [&](const int32_t *a, const int32_t *off) {
@@ -1569,8 +2059,7 @@ int32_t afh_restrict_tree(afh_tree *t, int32_t iv) {
   for (int l = t->nlvl - 1; l >= 1; l--) {
     const int n = t->children_of.n(l);
     if (!n) continue;
-    hipLaunchKernelGGL(k2_restrict, grid2(t->nc * t->nc / 4, n), blk2(t->nc * t->nc / 4), 0, t->stream,
-                       t->ccv(iv), t->d_boxes, t->children_of.at(l), t->nc, t->bsz);
+    restrict_boxes(t, t->ccv(iv), t->children_of.at(l), n, true);
     H2_LAUNCH("k2_restrict");
   }
   return AFH_OK;
@@ -1608,6 +2097,10 @@ int32_t afh_mg_create(afh_tree *t, const afh_mg_desc *d, afh_mg **out) {
   if (d->coarse_mode != AFH_COARSE_DIRECT &&
       !(d->coarse_mode == AFH_COARSE_PFMG && d->coarse_cycles >= 1 && d->coarse_tol >= 0))
     return set_error(AFH_ERR_UNSUPPORTED, "2-D: AFH_COARSE_DIRECT or AFH_COARSE_PFMG");
+  if (t->cyl() && d->coarse_mode == AFH_COARSE_DIRECT)
+    return set_error(AFH_ERR_UNSUPPORTED,
+                     "2-D cylindrical: AFH_COARSE_DIRECT's cosine / sine basis does not "
+                     "diagonalise the operator in r; use AFH_COARSE_PFMG");
   if (d->n_cycle_down < 1 || d->n_cycle_up < 1)
     return set_error(AFH_ERR_ARG, "afh_mg_create: cycles");
   const int nx = t->cgs[0], ny = t->cgs[1];
@@ -1616,6 +2109,7 @@ int32_t afh_mg_create(afh_tree *t, const afh_mg_desc *d, afh_mg **out) {
   afh_mg *mg = new afh_mg();
   mg->t = t;
   mg->d = *d;
+  t->coord_fixed = true;
   mg->nx = nx, mg->ny = ny;
   // mg_box_lpl_stencil: c(2:5) = 1/dr^2, c(1) = -sum(c(2:)) - lambda
   mg->lvl_c.resize(t->nlvl);
@@ -1716,6 +2210,13 @@ static int32_t solve_coarse_pfmg(afh_mg *mg) {
           const size_t g = (size_t)(gi[1] - 1) * nx + (gi[0] - 1);
           double c[7] = {mg->lvl_c[0].c[0], mg->lvl_c[0].c[1], mg->lvl_c[0].c[2],
                          mg->lvl_c[0].c[3], mg->lvl_c[0].c[4], 0.0, 0.0};
+          if (t->cyl()) {
+            // af_stencil_get_box's cylindrical coefficients of the cell
+            // (m_af_stencil.f90:1056-1066), before the boundaries are folded
+            double q4[4];
+            cyl_coef(mg->lvl_c[0], m.r_min[0], m.dr[0], i, q4);
+            c[0] = q4[0], c[1] = q4[1], c[2] = q4[2];
+          }
           for (int nb = 1; nb <= 4; nb++) {
             const int dd = (nb - 1) >> 1;
             const bool low = ((nb - 1) & 1) == 0;
@@ -1847,7 +2348,16 @@ static int32_t gsrb_boxes(afh_mg *mg, int lvl, bool up, bool skip_corners = fals
       const double *rh = t->ccv(mg->d.i_rhs);
       const int32_t *ids = t->ids.at(lvl);
       // several boxes per wave: four 4^2, two 8^2
-      if (t->nc == 4)
+      if (t->cyl() && t->nc == 4)
+        hipLaunchKernelGGL((k2_pair_box_cyl<4, 16>), dim3((n + 3) / 4), dim3(64), 0, t->stream,
+                           src, dst, rh, phi, t->d_boxes, ids, n, t->bsz, cf, g);
+      else if (t->cyl() && t->nc == 8)
+        hipLaunchKernelGGL((k2_pair_box_cyl<8, 32>), dim3((n + 1) / 2), dim3(64), 0, t->stream,
+                           src, dst, rh, phi, t->d_boxes, ids, n, t->bsz, cf, g);
+      else if (t->cyl())
+        hipLaunchKernelGGL(k2_pair_box_cyl<16>, dim3(n), dim3(64), 0, t->stream, src, dst, rh,
+                           phi, t->d_boxes, ids, n, t->bsz, cf, g);
+      else if (t->nc == 4)
         hipLaunchKernelGGL((k2_pair_box<4, 16>), dim3((n + 3) / 4), dim3(64), 0, t->stream, src,
                            dst, rh, phi, t->d_boxes, ids, n, t->bsz, cf, g);
       else if (t->nc == 8)
@@ -1873,6 +2383,11 @@ static int32_t gsrb_boxes(afh_mg *mg, int lvl, bool up, bool skip_corners = fals
       // levels' launches are launch-bound, another regime
       const int pc = n >= 256 ? AFH_PROF_GSRB : -1;
       prof_mark(t, pc);
+      if (t->cyl())
+        hipLaunchKernelGGL(k2_gsrb_cyl, grid2(t->nc * t->nc / 2, n), blk2(t->nc * t->nc / 2),
+                           cyl_lds(t), t->stream, t->ccv(mg->d.i_phi), t->ccv(mg->d.i_rhs),
+                           t->d_boxes, t->ids.at(lvl), t->nc, t->bsz, mg->lvl_c[lvl - 1], s);
+      else
       hipLaunchKernelGGL(k2_gsrb, grid2(t->nc * t->nc / 2, n), blk2(t->nc * t->nc / 2), 0, t->stream,
                          t->ccv(mg->d.i_phi), t->ccv(mg->d.i_rhs), t->ids.at(lvl), t->nc,
                          t->bsz, mg->lvl_c[lvl - 1], s);
@@ -1888,7 +2403,13 @@ static int32_t gsrb_boxes(afh_mg *mg, int lvl, bool up, bool skip_corners = fals
 static int32_t update_coarse(afh_mg *mg, int lvl) {
   afh_tree *t = mg->t;
   const int n = t->ids.n(lvl);
-  if (n) {
+  if (n && t->cyl()) {
+    hipLaunchKernelGGL(k2_rstr_fas_cyl, grid2(t->nc * t->nc / 4, n), blk2(t->nc * t->nc / 4),
+                       cyl_lds(t), t->stream, t->ccv(mg->d.i_phi), t->ccv(mg->d.i_rhs),
+                       t->ccv(mg->d.i_tmp), t->d_boxes, t->ids.at(lvl), t->nc, t->bsz,
+                       mg->lvl_c[lvl - 1]);
+    H2_LAUNCH("k2_rstr_fas_cyl");
+  } else if (n) {
     hipLaunchKernelGGL(k2_rstr_fas, grid2(t->nc * t->nc / 4, n), blk2(t->nc * t->nc / 4), 0, t->stream,
                        t->ccv(mg->d.i_phi), t->ccv(mg->d.i_rhs), t->ccv(mg->d.i_tmp),
                        t->d_boxes, t->ids.at(lvl), t->nc, t->bsz, mg->lvl_c[lvl - 1]);
@@ -1896,7 +2417,12 @@ static int32_t update_coarse(afh_mg *mg, int lvl) {
   }
   if (int32_t e = gc_lvl(t, lvl - 1, mg->d.i_phi, true)) return e;
   const int np = t->parents.n(lvl - 1);
-  if (np) {
+  if (np && t->cyl()) {
+    hipLaunchKernelGGL(k2_parent_rhs_cyl, grid2(t->bsz, np), blk2(t->bsz), cyl_lds(t), t->stream,
+                       t->ccv(mg->d.i_phi), t->ccv(mg->d.i_rhs), t->ccv(mg->d.i_tmp), t->d_boxes,
+                       t->parents.at(lvl - 1), t->nc, t->bsz, mg->lvl_c[lvl - 2], 1);
+    H2_LAUNCH("k2_parent_rhs_cyl");
+  } else if (np) {
     hipLaunchKernelGGL(k2_parent_rhs, grid2(t->bsz, np), blk2(t->bsz), 0, t->stream,
                        t->ccv(mg->d.i_phi), t->ccv(mg->d.i_rhs), t->ccv(mg->d.i_tmp),
                        t->parents.at(lvl - 1), t->nc, t->bsz, mg->lvl_c[lvl - 2], 1);
@@ -1931,6 +2457,12 @@ static int32_t residual_lvl(afh_mg *mg, int lvl, const LevelList &L, bool fold) 
   afh_tree *t = mg->t;
   const int n = L.n(lvl);
   if (!n) return AFH_OK;
+  if (t->cyl())
+    hipLaunchKernelGGL(k2_residual_cyl, grid2(t->nc * t->nc, n), blk2(t->nc * t->nc), cyl_lds(t),
+                       t->stream, t->ccv(mg->d.i_phi), t->ccv(mg->d.i_rhs), t->ccv(mg->d.i_tmp),
+                       L.at(lvl), t->nc, t->bsz, mg->lvl_c[lvl - 1],
+                       fold ? t->red + 3 * RED_SHARDS : nullptr, nullptr, t->d_boxes);
+  else
   hipLaunchKernelGGL(k2_residual, grid2(t->nc * t->nc, n), blk2(t->nc * t->nc), 0, t->stream,
                      t->ccv(mg->d.i_phi), t->ccv(mg->d.i_rhs), t->ccv(mg->d.i_tmp), L.at(lvl),
                      t->nc, t->bsz, mg->lvl_c[lvl - 1],
@@ -1945,7 +2477,12 @@ static bool residual_all(afh_mg *mg, int max_lvl, const LevelList &L, bool fold)
   afh_tree *t = mg->t;
   const int n = L.off[max_lvl] - L.off[0];
   if (!mg->all_lvl || n > 65535) return false;
-  if (n)
+  if (n && t->cyl())
+    hipLaunchKernelGGL(k2_residual_cyl, grid2(t->nc * t->nc, n), blk2(t->nc * t->nc), cyl_lds(t),
+                       t->stream, t->ccv(mg->d.i_phi), t->ccv(mg->d.i_rhs), t->ccv(mg->d.i_tmp),
+                       L.at(1), t->nc, t->bsz, mg->lvl_c[0],
+                       fold ? t->red + 3 * RED_SHARDS : nullptr, mg->d_lvl_c, t->d_boxes);
+  else if (n)
     hipLaunchKernelGGL(k2_residual, grid2(t->nc * t->nc, n), blk2(t->nc * t->nc), 0, t->stream,
                        t->ccv(mg->d.i_phi), t->ccv(mg->d.i_rhs), t->ccv(mg->d.i_tmp), L.at(1),
                        t->nc, t->bsz, mg->lvl_c[0], fold ? t->red + 3 * RED_SHARDS : nullptr,
@@ -2062,15 +2599,19 @@ int32_t afh_mg_fas_fmg(afh_mg *mg, int32_t set_residual, int32_t have_guess) {
       if ((e = residual_lvl(mg, l, t->ids, false))) return e;
       const int n = t->ids.n(l);
       if (n) {
-        hipLaunchKernelGGL(k2_restrict, grid2(nc * nc / 4, n), blk2(nc * nc / 4), 0, t->stream, tmp,
-                           t->d_boxes, t->ids.at(l), nc, t->bsz);
-        hipLaunchKernelGGL(k2_restrict, grid2(nc * nc / 4, n), blk2(nc * nc / 4), 0, t->stream, phi,
-                           t->d_boxes, t->ids.at(l), nc, t->bsz);
+        // mg_box_rstr_lpl: tmp with geometry, phi without
+        restrict_boxes(t, tmp, t->ids.at(l), n, true);
+        restrict_boxes(t, phi, t->ids.at(l), n, false);
         H2_LAUNCH("k2_restrict");
       }
       if ((e = gc_lvl(t, l - 1, mg->d.i_phi, true))) return e;
       const int np = t->parents.n(l - 1);
-      if (np) {
+      if (np && t->cyl()) {
+        hipLaunchKernelGGL(k2_parent_rhs_cyl, grid2(t->bsz, np), blk2(t->bsz), cyl_lds(t),
+                           t->stream, phi, rhs, tmp, t->d_boxes, t->parents.at(l - 1), nc, t->bsz,
+                           mg->lvl_c[l - 2], 0);
+        H2_LAUNCH("k2_parent_rhs_cyl");
+      } else if (np) {
         hipLaunchKernelGGL(k2_parent_rhs, grid2(t->bsz, np), blk2(t->bsz), 0, t->stream, phi, rhs,
                            tmp, t->parents.at(l - 1), nc, t->bsz, mg->lvl_c[l - 2], 0);
         H2_LAUNCH("k2_parent_rhs");
@@ -2084,8 +2625,7 @@ int32_t afh_mg_fas_fmg(afh_mg *mg, int32_t set_residual, int32_t have_guess) {
       hipLaunchKernelGGL(k2_block, grid2(t->bsz, n), blk2(t->bsz), 0, t->stream, phi,
                          (const double *)nullptr, (const double *)nullptr, t->ids.at(l),
                          t->bsz, 2);
-      hipLaunchKernelGGL(k2_restrict, grid2(nc * nc / 4, n), blk2(nc * nc / 4), 0, t->stream, rhs,
-                         t->d_boxes, t->ids.at(l), nc, t->bsz);
+      restrict_boxes(t, rhs, t->ids.at(l), n, true);
       H2_LAUNCH("k2_restrict");
     }
   }
@@ -2154,6 +2694,7 @@ int32_t afh_fluid_create(afh_tree *t, const afh_fluid_desc *d, afh_fluid **out) 
   afh_fluid *f = new afh_fluid();
   f->t = t;
   f->d = *d;
+  t->coord_fixed = true;
   f->d.reactions = nullptr;
   const size_t ntd = (size_t)d->td.n_points * d->td.n_cols;
   const size_t nch = (size_t)d->chem.n_points * d->chem.n_cols;
@@ -2246,8 +2787,7 @@ static int32_t flux_tree(afh_fluid *f, int32_t s_deriv, double *dt_lim, bool fet
   for (int l = 1; l <= t->nlvl; l++) {
     const int n = t->refb.n(l);
     if (!n) continue;
-    hipLaunchKernelGGL(k2_restrict, grid2(nc * nc / 4, n), blk2(nc * nc / 4), 0, t->stream,
-                       t->ccv(iv), t->d_boxes, t->refb.at(l), nc, t->bsz);
+    restrict_boxes(t, t->ccv(iv), t->refb.at(l), n, true);
     H2_LAUNCH("k2_restrict");
   }
   int32_t e;
@@ -2276,7 +2816,11 @@ static int32_t flux_tree(afh_fluid *f, int32_t s_deriv, double *dt_lim, bool fet
   }
   // af_consistent_fluxes
   const int ntask = t->cflux.off.back();
-  if (ntask) {
+  if (ntask && t->cyl()) {
+    hipLaunchKernelGGL(k2_consistent_cyl, dim3((ntask * nc + NT - 1) / NT), dim3(NT), 0,
+                       t->stream, t->fcv(f->d.f_flux), t->d_boxes, t->cflux.d, ntask, nc, t->fsz);
+    H2_LAUNCH("k2_consistent_cyl");
+  } else if (ntask) {
     hipLaunchKernelGGL(k2_consistent, dim3((ntask * nc + NT - 1) / NT), dim3(NT), 0, t->stream,
                        t->fcv(f->d.f_flux), t->d_boxes, t->cflux.d, ntask, nc, t->fsz);
     H2_LAUNCH("k2_consistent");
@@ -2321,6 +2865,18 @@ static int32_t update(afh_fluid *f, double dt, int32_t s_deriv, int32_t n_prev,
     const dim3 bk = blk2(t->nc * t->nc);
     const int32_t *ids = t->leaves.at(l);
     unsigned long long *red = t->red + 2 * RED_SHARDS;
+    if (t->cyl()) {
+      switch (A.ns) {
+#define AFH2_UPD(N) \
+  case N: hipLaunchKernelGGL(k2_update_cyl<N>, g, bk, 0, t->stream, A, ids, t->d_boxes, t->nc, t->bsz, t->fsz, red); break;
+        AFH2_UPD(1) AFH2_UPD(2) AFH2_UPD(3) AFH2_UPD(4) AFH2_UPD(5) AFH2_UPD(6) AFH2_UPD(7)
+        AFH2_UPD(8) AFH2_UPD(9) AFH2_UPD(10) AFH2_UPD(11) AFH2_UPD(12)
+#undef AFH2_UPD
+      default:
+        hipLaunchKernelGGL(k2_update_cyl<MAXS>, g, bk, 0, t->stream, A, ids, t->d_boxes, t->nc,
+                           t->bsz, t->fsz, red);
+      }
+    } else
     switch (A.ns) {
 #define AFH2_UPD(N) \
   case N: hipLaunchKernelGGL(k2_update<N>, g, bk, 0, t->stream, A, ids, t->d_boxes, t->nc, t->bsz, t->fsz, red); break;
@@ -2640,6 +3196,27 @@ __global__ void __launch_bounds__(NT)
   out[2 * q + 1] = (double)bix;
 }
 
+// sum_2pr_box (m_af_utils.f90:1008-1024): res = res + cc**power * r_i in the
+// Fortran element order, then res * 2 pi
+__global__ void __launch_bounds__(NT)
+    k2_box_sum_cyl(const double *__restrict__ v, const afh_box_meta *__restrict__ meta,
+                   const int32_t *__restrict__ ids, int nl, int nc, int bsz, int power,
+                   double *__restrict__ out) {
+  const int q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= nl) return;
+  const int id = ids[q];
+  const double *c = v + (size_t)(id - 1) * bsz;
+  const double r_min = meta[id - 1].r_min[0], dr = meta[id - 1].dr[0];
+  const double twopi = 2 * 3.141592653589793;  // 2 * acos(-1.0_dp)
+  const int ng = nc + 2;
+  double res = 0.0;
+  for (int j = 1; j <= nc; j++)
+    for (int i = 1; i <= nc; i++)
+      res = res + ipow2(c[ix2(ng, i, j)], power) * (r_min + (i - 0.5) * dr);
+  out[2 * q] = res * twopi;
+  out[2 * q + 1] = -1.0;
+}
+
 static int32_t device_list(const std::vector<int32_t> &h, int32_t **d) {
   H2(hipMalloc(d, sizeof(int32_t) * std::max<size_t>(1, h.size())));
   if (!h.empty())
@@ -2656,8 +3233,12 @@ static int32_t box_reduce(afh_tree *t, int iv, int op, int power, std::vector<do
   const double *v = t->ccv(iv);
   switch (op) {
   case 0:
-    hipLaunchKernelGGL(k2_box_reduce<0>, grid, blk, 0, t->stream, v, t->leaves.d, nl, t->nc,
-                       t->bsz, power, t->d_boxred);
+    if (t->coord == AFH_COORD_CYL)
+      hipLaunchKernelGGL(k2_box_sum_cyl, grid, blk, 0, t->stream, v, t->d_boxes, t->leaves.d, nl,
+                         t->nc, t->bsz, power, t->d_boxred);
+    else
+      hipLaunchKernelGGL(k2_box_reduce<0>, grid, blk, 0, t->stream, v, t->leaves.d, nl, t->nc,
+                         t->bsz, power, t->d_boxred);
     break;
   case AFH_RED_MAX:
     hipLaunchKernelGGL(k2_box_reduce<AFH_RED_MAX>, grid, blk, 0, t->stream, v, t->leaves.d, nl,
@@ -2726,8 +3307,7 @@ int32_t afh_tree_regrid(afh_tree *o, const afh_tree_desc *d, afh_tree **out) {
   if (!rchild.empty()) {
     if ((e = device_list(rchild, &d_list))) return e;
     for (int iv : o->auto_vars) {
-      hipLaunchKernelGGL(k2_restrict, grid2(nc * nc / 4, (int)rchild.size()), blk2(nc * nc / 4), 0,
-                         o->stream, o->ccv(iv), o->d_boxes, d_list, nc, o->bsz);
+      restrict_boxes(o, o->ccv(iv), d_list, (int)rchild.size(), true);
       H2_LAUNCH("k2_restrict");
     }
     H2(hipStreamSynchronize(o->stream));
@@ -2738,6 +3318,7 @@ int32_t afh_tree_regrid(afh_tree *o, const afh_tree_desc *d, afh_tree **out) {
   if ((e = afh_tree_create(d, o->device, &t))) return e;
   t->meth = o->meth;
   t->auto_vars = o->auto_vars;
+  t->coord = o->coord;
   if (!kept.empty()) {
     if ((e = device_list(kept, &d_list))) return e;
     const unsigned n = (unsigned)kept.size();
@@ -2824,9 +3405,10 @@ int32_t afh_refine_flags(afh_fluid *f, const afh_refine_desc *d, const uint8_t *
   return AFH_OK;
 }
 
-// af_tree_sum_cc (m_af_utils.f90:966-1026), Cartesian: per leaf the sum of
-// cc**power, then my_sum = my_sum + fac * tmp in the reference's loop order
-// (levels, then leaves), fac = product(af_lvl_dr)
+// af_tree_sum_cc (m_af_utils.f90:966-1026): per leaf the sum of cc**power
+// (af_cyl: sum_2pr_box, 2 pi sum cc**power r_i), then my_sum = my_sum + fac *
+// tmp in the reference's loop order (levels, then leaves), fac =
+// product(af_lvl_dr)
 int32_t afh_tree_sum_cc(afh_tree *t, int32_t iv, int32_t power, double *out) {
   if (int32_t e = check_iv(t, iv, "afh_tree_sum_cc")) return e;
   if (power < 1 || !out) return set_error(AFH_ERR_ARG, "afh_tree_sum_cc: bad argument");

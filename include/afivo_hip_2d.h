@@ -27,10 +27,12 @@
  * restated (AFH_COARSE_PFMG, round 5), the field gradient and
  * |E|, field_set_rhs, the species step (af_restrict_ref_boundary, af_gc2_box,
  * flux_upwind_box with the m_fluid callbacks, af_consistent_fluxes,
- * flux_update_densities with the field-dependent rate forms). Not built in
- * 2-D (AFH_ERR_UNSUPPORTED or not exported): cylindrical coordinates
- * (af_cyl), electrodes / level sets, variable gas density, photoionization,
- * the temperature rate forms, sharding, ion secondary emission. Built in
+ * flux_update_densities with the field-dependent rate forms), and all of it
+ * in cylindrical coordinates (af_cyl: first index r, second z; selected per
+ * tree with afh_tree_set_coord, afivo_hip_2d_cyl.h). Not built in 2-D
+ * (AFH_ERR_UNSUPPORTED or not exported): electrodes / level sets, variable
+ * gas density, photoionization, the temperature rate forms, sharding, ion
+ * secondary emission, AFH_COARSE_DIRECT on a cylindrical tree. Built in
  * round 4 for the 2-D time loop (afh.driver over this library,
  * programs/standard_2d/tests/test_2d_rtest.log): the device regrid with the
  * prolongation of the automatic variables, default_refinement's flags, the
@@ -42,6 +44,8 @@
 #define AFIVO_HIP_2D_H
 
 #include "afivo_hip.h"
+/* the entry points only the 2-D library has (cylindrical coordinates) */
+#include "afivo_hip_2d_cyl.h"
 
 #ifdef __cplusplus
 extern "C" {
