@@ -259,7 +259,8 @@ class Simulation:
         # the Helmholtz modes 1 .. n-1 get an rhs and a tmp variable of their
         # own (after the reference's variables): afh_photoi_helmh_compute then
         # solves the modes concurrently, bitwise the one-after-another solve
-        # (AFH_HELMH_CONC=0: the shared variables, modes in turn)
+        # (AFH_HELMH_CONC=0: the shared variables, modes in turn; the 2-D
+        # library takes either layout and solves the modes in turn)
         self.n_scratch = 0
         if self.photoi and os.environ.get("AFH_HELMH_CONC", "1") != "0":
             self.n_scratch = 2 * (len(BOURDON3_LAMBDAS) - 1)
@@ -750,8 +751,10 @@ class Simulation:
 
     def _set_methods(self, t):
         neumann0 = [(capi.BC_NEUMANN, 0.0)] * 6
-        # z faces Dirichlet 0, other faces Neumann 0 (photoi_helmh_bc)
-        helm_bc = [(capi.BC_NEUMANN, 0.0)] * 4 + [(capi.BC_DIRICHLET, 0.0)] * 2
+        # the faces normal to the last dimension Dirichlet 0, the other faces
+        # Neumann 0 (photoi_helmh_bc)
+        helm_bc = ([(capi.BC_NEUMANN, 0.0)] * (2 * self.ndim - 2) +
+                   [(capi.BC_DIRICHLET, 0.0)] * 2)
         if self.photoi:  # photoi_initialize (m_photoi.f90:105-106): first auto var
             t.set_cc_methods(self.i_photo, helm_bc, capi.RB_GC_INTERP)
             t.set_cc_prolong(self.i_photo, capi.PROLONG_LINEAR)

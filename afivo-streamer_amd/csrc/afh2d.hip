@@ -38,7 +38,11 @@
 //                 m_fluid callbacks (src/m_fluid.f90:102-227), Koren
 //   k2_consistent af_consistent_fluxes / flux_from_children (m_af_core.f90:1257-1357)
 //   k2_update     flux_update_densities (m_af_flux_schemes.f90:320-394) +
-//                 add_source_terms / get_rates / get_derivatives (field forms)
+//                 add_source_terms / get_rates / get_derivatives (field forms);
+//                 k2_update_photo with the photoionization rate (m_fluid.f90:435-440)
+//   k2_photoi_src photoionization_rate_from_alpha (src/m_photoi.f90:232-270)
+//   k2_photoi_sum photoi_helmh_compute's clear and per-mode subtraction
+//                 (src/m_photoi_helmh.f90:169, 191-202)
 //
 // Cylindrical coordinates (af_cyl, afh_tree_set_coord): k2_gsrb_cyl,
 // k2_pair_box_cyl, k2_residual_cyl, k2_rstr_fas_cyl, k2_parent_rhs_cyl (the
@@ -49,6 +53,7 @@
 // m_af_utils.f90:1008-1024) and the per-cell PFMG level-1 coefficients. They
 // are separate kernels: a Cartesian tree launches exactly what it did before.
 #include <hip/hip_runtime.h>
+#include <float.h>
 #include <math.h>
 #include <stdarg.h>
 #include <stdint.h>
@@ -1465,11 +1470,20 @@ __global__ void __launch_bounds__(NT)
 // The update once more for a cylindrical tree (k2_update_cyl, CYL = true the
 // only instantiation; k2_update above keeps its own text): the r-fluxes times
 // af_cyl_flux_factors inside the divergence (m_af_flux_schemes.f90:395-406)
-template <int NS, bool CYL>
+// PHOTO (k2_update_photo, k2_update_cyl_photo; a fluid with i_photo > 0): the
+// photoionization rate P.photo added to the derivative of the electrons and
+// of species slot P.s after the chemistry limit (m_fluid.f90:435-440). The
+// kernels of a fluid without it take no such argument and keep their code.
+struct PhotoArgs {
+  const double *photo;
+  int s;
+};
+
+template <int NS, bool CYL, bool PHOTO = false>
 __device__ __forceinline__ void
 update_body(UpdArgs A, const int32_t *__restrict__ ids,
             const afh_box_meta *__restrict__ meta, int nc, int bsz, int fsz,
-            unsigned long long *red) {
+            unsigned long long *red, PhotoArgs P = PhotoArgs{nullptr, 0}) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   double cmin = 1e100;
   const int ns = NS == MAXS ? A.ns : NS;
@@ -1514,6 +1528,11 @@ update_body(UpdArgs A, const int32_t *__restrict__ ids,
         cmin = fmin(cmin, a / b);
       }
     }
+    if (PHOTO) {
+      const double pho = P.photo[x];
+      der[A.e_index] = der[A.e_index] + pho;
+      der[P.s] = der[P.s] + pho;
+    }
 #pragma unroll
     for (int s = 0; s < ns; s++) y[s] = y[s] + A.dt * der[s];
     const double *F = A.F + (size_t)(id - 1) * fsz;
@@ -1540,6 +1559,85 @@ __global__ void __launch_bounds__(NT)
                   const afh_box_meta *__restrict__ meta, int nc, int bsz, int fsz,
                   unsigned long long *red) {
   update_body<NS, true>(A, ids, meta, nc, bsz, fsz, red);
+}
+
+template <int NS>
+__global__ void __launch_bounds__(NT)
+    k2_update_photo(UpdArgs A, const int32_t *__restrict__ ids,
+                    const afh_box_meta *__restrict__ meta, int nc, int bsz, int fsz,
+                    unsigned long long *red, PhotoArgs P) {
+  update_body<NS, false, true>(A, ids, meta, nc, bsz, fsz, red, P);
+}
+
+template <int NS>
+__global__ void __launch_bounds__(NT)
+    k2_update_cyl_photo(UpdArgs A, const int32_t *__restrict__ ids,
+                        const afh_box_meta *__restrict__ meta, int nc, int bsz, int fsz,
+                        unsigned long long *red, PhotoArgs P) {
+  update_body<NS, true, true>(A, ids, meta, nc, bsz, fsz, red, P);
+}
+
+// photoionization_rate_from_alpha (src/m_photoi.f90:232-270) with a constant
+// gas density: one thread per leaf interior cell, the leaves of every level
+// in one launch (ids: the concatenated leaf list, n boxes); operand order as
+// there, the table location as LT_get_loc
+__global__ void __launch_bounds__(NT)
+    k2_photoi_src(double *__restrict__ rhs, const double *__restrict__ E,
+                  const double *__restrict__ ne, double gas_dens, DevLT td, int alpha_col,
+                  double coeff, const int32_t *__restrict__ ids, int n, int nc, int bsz) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  const int ncell = nc * nc;
+  if (t >= n * ncell) return;
+  const int b = t / ncell, c = t % ncell;
+  const size_t x = (size_t)(ids[b] - 1) * bsz + ix2(nc + 2, c % nc + 1, c / nc + 1);
+  const double fld = E[x];
+  const double Td = fld * 1e21 / gas_dens;
+  const double frac = (Td - td.x_min) * td.inv_fac;
+  int low;
+  double lf;
+  if (frac <= 0) {
+    low = 1;
+    lf = 1;
+  } else if (frac >= td.n_points - 1) {
+    low = td.n_points - 1;
+    lf = 0;
+  } else {
+    low = (int)ceil(frac);
+    lf = low - frac;
+  }
+  const double *ra = td.rc + (size_t)(alpha_col - 1) * td.n_points + (low - 1);
+  const double *rm = td.rc + (low - 1);
+  const double alpha = lf * ra[0] + (1 - lf) * ra[1];
+  const double mobility = lf * rm[0] + (1 - lf) * rm[1];
+  double tmp = fld * mobility * alpha * ne[x] * coeff;
+  if (tmp < 0) tmp = 0;
+  rhs[x] = tmp;
+}
+
+// photoi_helmh_compute's sum (m_photoi_helmh.f90:169, 191-202) over whole box
+// images, ghost cells included, of every box in one launch: af_tree_clear_cc
+// and then, per mode in order, cc(i_photo) = cc(i_photo) - coeffs(n) * phi_n
+// on the leaves. first: the value starts from the clear (a non-leaf box gets
+// +0.0, a leaf 0.0 - c_1 phi_1 - ..., the signed zeros of the separate
+// passes); otherwise from the stored value (modes 5.. of a longer list)
+struct SumArgs {
+  const double *phi[4];
+  double c[4];
+  int n;
+};
+
+__global__ void __launch_bounds__(NT)
+    k2_photoi_sum(double *__restrict__ out, SumArgs S, const uint8_t *__restrict__ leaf,
+                  int bsz, size_t total, int first) {
+  const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= total) return;
+  if (!leaf[q / bsz]) {
+    if (first) out[q] = 0.0;
+    return;
+  }
+  double v = first ? 0.0 : out[q];
+  for (int m = 0; m < S.n; m++) v = v - S.c[m] * S.phi[m][q];
+  out[q] = v;
 }
 
 __global__ void k2_red_fill(unsigned long long *red, unsigned long long v) {
@@ -1621,6 +1719,7 @@ struct afh_tree {
   std::vector<int> auto_vars;  // tree%cc_auto_vars (afh_set_cc_prolong order)
   std::vector<double> lvl_dr;  // 2 per level
   double *d_boxred = nullptr;  // per-leaf (value, cell) of afh_tree_sum_cc / reduce_loc
+  uint8_t *d_leaf = nullptr;   // per box id: a leaf (k2_photoi_sum; made on first use)
   // kernel timing (afh_profile_enable/read, as in libafivo_hip): HIP events
   // around every launch of one kernel class on the tree's stream
   int prof_class = 0;
@@ -1927,6 +2026,7 @@ int32_t afh_tree_destroy(afh_tree *t) {
     free_list(*L);
   hipFree(t->d_boxes), hipFree(t->cc), hipFree(t->fc), hipFree(t->gc2);
   hipFree(t->red), hipFree(t->red_out), hipHostFree(t->h_red), hipFree(t->d_boxred);
+  hipFree(t->d_leaf);
   for (hipEvent_t e : t->ev_pool) hipEventDestroy(e);
   hipStreamDestroy(t->stream);
   delete t;
@@ -2682,9 +2782,11 @@ int32_t afh_fluid_create(afh_tree *t, const afh_fluid_desc *d, afh_fluid **out) 
   if (!t || !d || !out) return set_error(AFH_ERR_ARG, "afh_fluid_create: null");
   if (d->n_species < 1 || d->n_species > AFH_MAX_SPECIES)
     return set_error(AFH_ERR_ARG, "afh_fluid_create: n_species");
-  if (d->i_gas_dens || d->i_photo || d->n_ions)
-    return set_error(AFH_ERR_UNSUPPORTED,
-                     "2-D: variable gas density / photoionization / mobile ions");
+  if (d->i_gas_dens || d->n_ions)
+    return set_error(AFH_ERR_UNSUPPORTED, "2-D: variable gas density / mobile ions");
+  if (d->i_photo < 0 || d->i_photo > t->nvc ||
+      (d->i_photo > 0 && (d->photo_species < 1 || d->photo_species > d->n_species)))
+    return set_error(AFH_ERR_ARG, "bad photoionization variable / species");
   for (int r = 0; r < d->n_reactions; r++) {
     const int ty = d->reactions[r].rate_type;
     if (ty != AFH_RATE_TABULATED_FIELD && ty != AFH_RATE_CONSTANT && ty != AFH_RATE_LINEAR &&
@@ -2865,7 +2967,26 @@ static int32_t update(afh_fluid *f, double dt, int32_t s_deriv, int32_t n_prev,
     const dim3 bk = blk2(t->nc * t->nc);
     const int32_t *ids = t->leaves.at(l);
     unsigned long long *red = t->red + 2 * RED_SHARDS;
-    if (t->cyl()) {
+    if (f->d.i_photo > 0) {
+      // the sibling kernels with the photoionization term
+      const PhotoArgs P{t->ccv(f->d.i_photo), f->d.photo_species - 1};
+      const bool cyl = t->cyl();
+      switch (A.ns) {
+#define AFH2_UPD(N)                                                                         \
+  case N:                                                                                   \
+    if (cyl)                                                                                \
+      hipLaunchKernelGGL(k2_update_cyl_photo<N>, g, bk, 0, t->stream, A, ids, t->d_boxes,   \
+                         t->nc, t->bsz, t->fsz, red, P);                                    \
+    else                                                                                    \
+      hipLaunchKernelGGL(k2_update_photo<N>, g, bk, 0, t->stream, A, ids, t->d_boxes,       \
+                         t->nc, t->bsz, t->fsz, red, P);                                    \
+    break;
+        AFH2_UPD(1) AFH2_UPD(2) AFH2_UPD(3) AFH2_UPD(4) AFH2_UPD(5) AFH2_UPD(6) AFH2_UPD(7)
+        AFH2_UPD(8) AFH2_UPD(9) AFH2_UPD(10) AFH2_UPD(11) AFH2_UPD(12)
+      default: AFH2_UPD(MAXS)
+#undef AFH2_UPD
+      }
+    } else if (t->cyl()) {
       switch (A.ns) {
 #define AFH2_UPD(N) \
   case N: hipLaunchKernelGGL(k2_update_cyl<N>, g, bk, 0, t->stream, A, ids, t->d_boxes, t->nc, t->bsz, t->fsz, red); break;
@@ -2958,6 +3079,85 @@ int32_t afh_fluid_fetch_step(afh_fluid *f, int32_t last_step, int32_t n_extra,
   dt_lim[2] = last_step ? r[2] : 1e100;
   dt_lim[3] = 1e100;
   if (n_extra) extra[0] = r[3];
+  return AFH_OK;
+}
+
+// photoi_set_src's Zheleznyak source (src/m_photoi.f90:232-270) on the leaf
+// interiors, one launch for the whole tree
+int32_t afh_photoi_set_src(afh_fluid *f, int32_t i_rhs, int32_t alpha_col, double coeff) {
+  if (!f) return set_error(AFH_ERR_ARG, "afh_photoi_set_src: null");
+  afh_tree *t = f->t;
+  if (i_rhs < 1 || i_rhs > t->nvc || alpha_col < 1 || alpha_col > f->d.td.n_cols)
+    return set_error(AFH_ERR_ARG, "afh_photoi_set_src: bad argument");
+  const int n = t->leaves.off[t->nlvl] - t->leaves.off[0];
+  if (!n) return AFH_OK;
+  const long long work = (long long)n * t->nc * t->nc;
+  // (the kernel's thread index is an int, the last workgroup included)
+  if (work > 0x7fffffffLL - NT)
+    return set_error(AFH_ERR_UNSUPPORTED, "afh_photoi_set_src: %d leaves", n);
+  hipLaunchKernelGGL(k2_photoi_src, dim3((unsigned)((work + NT - 1) / NT)), dim3(NT), 0, t->stream,
+                     t->ccv(i_rhs), t->ccv(f->d.i_efld), t->ccv(f->d.i_electron),
+                     f->d.gas_number_density, dev_lt(f->d.td, f->d_td), alpha_col, coeff,
+                     t->leaves.at(1), n, t->nc, t->bsz);
+  H2_LAUNCH("k2_photoi_src");
+  return AFH_OK;
+}
+
+// photoi_helmh_compute (src/m_photoi_helmh.f90:162-204): the modes one after
+// another on the tree's stream, then the sum of all of them in one launch
+// (k2_photoi_sum; the reference subtracts after each mode, the same values)
+int32_t afh_photoi_helmh_compute(afh_mg *const *modes, int32_t n_modes, const double *coeffs,
+                                 int32_t i_photo, double max_rel_res, int32_t max_fmg,
+                                 int32_t *n_fmg) {
+  if (!modes || n_modes < 1 || !coeffs || max_fmg < 1)
+    return set_error(AFH_ERR_ARG, "afh_photoi_helmh_compute: bad argument");
+  afh_tree *t = modes[0] ? modes[0]->t : nullptr;
+  if (!t) return set_error(AFH_ERR_ARG, "afh_photoi_helmh_compute: null mode");
+  for (int n = 0; n < n_modes; n++)
+    if (!modes[n] || modes[n]->t != t)
+      return set_error(AFH_ERR_ARG, "helmholtz modes must share one tree");
+  if (i_photo < 1 || i_photo > t->nvc) return set_error(AFH_ERR_ARG, "bad i_photo");
+  const size_t total = (size_t)t->nb * t->bsz;
+  // the source is the last mode's rhs (photoi_set_src's i_rhs); a mode with
+  // an rhs of its own gets a copy
+  const int src = modes[n_modes - 1]->d.i_rhs;
+  for (int n = 0; n + 1 < n_modes; n++)
+    if (modes[n]->d.i_rhs != src)
+      H2(hipMemcpyAsync(t->ccv(modes[n]->d.i_rhs), t->ccv(src), sizeof(double) * total,
+                        hipMemcpyDeviceToDevice, t->stream));
+  int32_t e;
+  double max_rhs;
+  if ((e = afh_tree_maxabs_cc(t, src, &max_rhs))) return e;
+  max_rhs = std::max(max_rhs, std::sqrt(DBL_EPSILON));
+  for (int n = 0; n < n_modes; n++) {
+    int i;
+    for (i = 1; i <= max_fmg; i++) {
+      double residu;
+      if ((e = afh_mg_fas_fmg(modes[n], 1, 1)) ||
+          (e = afh_tree_maxabs_cc(t, modes[n]->d.i_tmp, &residu)))
+        return e;
+      if (residu / max_rhs < max_rel_res) break;
+    }
+    if (n_fmg) n_fmg[n] = std::min(i, max_fmg);
+  }
+  if (!t->d_leaf) {
+    std::vector<uint8_t> leaf(t->nb, 0);
+    for (const auto &lv : t->h_leaves)
+      for (int id : lv) leaf[id - 1] = 1;
+    H2(hipMalloc(&t->d_leaf, t->nb));
+    H2(hipMemcpy(t->d_leaf, leaf.data(), t->nb, hipMemcpyHostToDevice));
+  }
+  for (int n0 = 0; n0 < n_modes; n0 += 4) {
+    SumArgs S;
+    S.n = std::min(4, n_modes - n0);
+    for (int m = 0; m < 4; m++) {
+      S.phi[m] = m < S.n ? t->ccv(modes[n0 + m]->d.i_phi) : nullptr;
+      S.c[m] = m < S.n ? coeffs[n0 + m] : 0.0;
+    }
+    hipLaunchKernelGGL(k2_photoi_sum, dim3((unsigned)((total + NT - 1) / NT)), dim3(NT), 0,
+                       t->stream, t->ccv(i_photo), S, t->d_leaf, t->bsz, total, n0 == 0);
+    H2_LAUNCH("k2_photoi_sum");
+  }
   return AFH_OK;
 }
 

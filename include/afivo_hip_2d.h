@@ -29,9 +29,12 @@
  * flux_upwind_box with the m_fluid callbacks, af_consistent_fluxes,
  * flux_update_densities with the field-dependent rate forms), and all of it
  * in cylindrical coordinates (af_cyl: first index r, second z; selected per
- * tree with afh_tree_set_coord, afivo_hip_2d_cyl.h). Not built in 2-D
+ * tree with afh_tree_set_coord, afivo_hip_2d_cyl.h), and Helmholtz
+ * photoionization with the Zheleznyak source (afh_photoi_set_src,
+ * afh_photoi_helmh_compute, the i_photo term of the species step; the source
+ * needs a constant gas density). Not built in 2-D
  * (AFH_ERR_UNSUPPORTED or not exported): electrodes / level sets, variable
- * gas density, photoionization, the temperature rate forms, sharding, ion
+ * gas density, the temperature rate forms, sharding, ion
  * secondary emission, AFH_COARSE_DIRECT on a cylindrical tree. Built in
  * round 4 for the 2-D time loop (afh.driver over this library,
  * programs/standard_2d/tests/test_2d_rtest.log): the device regrid with the
@@ -118,6 +121,17 @@ int32_t afh_fluid_forward_euler_fold(afh_fluid *f, double dt, int32_t s_deriv,
                                      int32_t last_step, int32_t store_flux);
 int32_t afh_fluid_fetch_step(afh_fluid *f, int32_t last_step, int32_t n_extra,
                              const int32_t *extra_slots, double *dt_lim, double *extra);
+/* Photoionization, as afivo_hip.h: the Zheleznyak source on the leaf interiors
+ * (constant gas density: gas_number_density) in one launch, and
+ * photoi_helmh_compute's mode loop -- the modes one after another on the
+ * tree's stream, a mode whose i_rhs is not the last mode's gets a copy of the
+ * source first -- with the sum of the modes into i_photo in one launch over
+ * every box (non-leaf boxes cleared). A fluid with i_photo > 0 adds cc(i_photo)
+ * to the derivatives of the electrons and of photo_species. */
+int32_t afh_photoi_set_src(afh_fluid *f, int32_t i_rhs, int32_t alpha_col, double coeff);
+int32_t afh_photoi_helmh_compute(afh_mg *const *modes, int32_t n_modes,
+                                 const double *coeffs, int32_t i_photo,
+                                 double max_rel_res, int32_t max_fmg, int32_t *n_fmg);
 
 #ifdef __cplusplus
 }
