@@ -57,14 +57,20 @@ def norm2(v):
 
 
 def _dot3(a, b):
-    return a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1] + a[..., 2] * b[..., 2]
+    """dot_product over the last axis (2 or 3 entries), left to right."""
+    s = a[..., 0] * b[..., 0]
+    for q in range(1, a.shape[-1]):
+        s = s + a[..., q] * b[..., q]
+    return s
 
 
 def dist_line(r, r0, r1):
-    """GM_dist_line (m_geometry.f90:23-51) at points r (..., 3)."""
+    """GM_dist_line (m_geometry.f90:23-51) at points r (..., ndim)."""
     r = np.asarray(r, float)
     d = r1 - r0
-    line_len2 = d[0] * d[0] + d[1] * d[1] + d[2] * d[2]
+    line_len2 = d[0] * d[0]
+    for q in range(1, len(d)):
+        line_len2 = line_len2 + d[q] * d[q]
     frac = _dot3(r - r0, d)
     lo, hi = frac <= 0.0, frac >= line_len2
     mid = r - (r0 + (frac / line_len2)[..., None] * d)
@@ -99,21 +105,23 @@ class SphereLSF:
 
 def cell_centers(r_min, dr, nc, lo=1, hi=None):
     """af_r_cc (m_af_types.f90:1035-1040) for cells lo..hi of a box, as an
-    array [k][j][i][3]."""
+    array [k][j][i][3] (NDIM = len(r_min) = 3) or [j][i][2] (NDIM = 2)."""
     hi = nc if hi is None else hi
+    nd = len(r_min)
     ix = np.arange(lo, hi + 1) - 0.5
-    r = np.empty((len(ix),) * 3 + (3,))
-    r[..., 0] = r_min[0] + ix[None, None, :] * dr[0]
-    r[..., 1] = r_min[1] + ix[None, :, None] * dr[1]
-    r[..., 2] = r_min[2] + ix[:, None, None] * dr[2]
+    r = np.empty((len(ix),) * nd + (nd,))
+    for d in range(nd):
+        sh = [1] * nd
+        sh[nd - 1 - d] = len(ix)  # dimension d varies along axis nd - 1 - d
+        r[..., d] = r_min[d] + ix.reshape(sh) * dr[d]
     return r
 
 
 def numerical_gradient(f, r):
-    """numerical_gradient (m_af_multigrid.f90:2144-2170) at points r (n, 3)."""
+    """numerical_gradient (m_af_multigrid.f90:2144-2170) at points r (n, ndim)."""
     step = np.maximum(EPS, SQRT_EPS * np.abs(r))
     g = np.empty_like(r)
-    for d in range(3):
+    for d in range(r.shape[1]):
         e = r.copy()
         e[:, d] = r[:, d] - step[:, d]
         flo = f(e)
@@ -238,15 +246,21 @@ def boxes_operators(f, boxes, nc, boundary_value):
     [k][j][i][7] the variable 7-point stencil, f_bc [k][j][i] the
     bc_correction (f times boundary_value), ix (n, 3) the 1-based cells with
     a boundary neighbour and dd (n, 6) their distances (the
-    mg_lsf_distance_key stencil that mg_box_lpllsf_gradient reads)."""
+    mg_lsf_distance_key stencil that mg_box_lpllsf_gradient reads).
+
+    NDIM is the length of the boxes' r_min: with 2, lsf_cells is [j][i], v
+    [j][i][5], f_bc [j][i], ix (n, 2), dd (n, 4) -- 2 NDIM neighbours and a
+    2 NDIM + 1 stencil (Cartesian: the cylindrical term of
+    mg_box_lsf_stencil, 1813-1821, is not restated)."""
     nb_ = len(boxes)
-    n3 = nc * nc * nc
-    rmins = np.array([np.asarray(b[1], float) for b in boxes]).reshape(nb_, 3)
-    drs = np.array([np.asarray(b[2], float) for b in boxes]).reshape(nb_, 3)
     out = [None] * nb_
     if not nb_:
         return out
-    cen = np.concatenate([cell_centers(rmins[q], drs[q], nc).reshape(-1, 3)
+    nd = len(boxes[0][1])
+    n3 = nc ** nd
+    rmins = np.array([np.asarray(b[1], float) for b in boxes]).reshape(nb_, nd)
+    drs = np.array([np.asarray(b[2], float) for b in boxes]).reshape(nb_, nd)
+    cen = np.concatenate([cell_centers(rmins[q], drs[q], nc).reshape(-1, nd)
                           for q in range(nb_)])  # per box k, j, i order
     lsf = np.concatenate([np.asarray(b[0], float).reshape(-1) for b in boxes])
     box_of = np.repeat(np.arange(nb_), n3)
@@ -260,10 +274,10 @@ def boxes_operators(f, boxes, nc, boundary_value):
     a = cen[im]
     bq = box_of[im]
     cell = im - bq * n3
-    kji = np.stack(np.unravel_index(cell, (nc, nc, nc)), axis=1)
+    kji = np.stack(np.unravel_index(cell, (nc,) * nd), axis=1)
     ijk0 = kji[:, ::-1] + 1
-    dd = np.ones((len(im), 6))
-    for nb in range(6):
+    dd = np.ones((len(im), 2 * nd))
+    for nb in range(2 * nd):
         d, sgn = nb // 2, -1 if nb % 2 == 0 else 1
         b = a.copy()
         # af_r_cc of the neighbour cell (its own index, not a + dr)
@@ -302,27 +316,28 @@ def boxes_operators(f, boxes, nc, boundary_value):
     for q in np.unique(bq[keep]):
         sel = keep & (bq == q)
         ix_cells = cell[sel]
-        kji = np.stack(np.unravel_index(ix_cells, (nc, nc, nc)), axis=1)
+        kji = np.stack(np.unravel_index(ix_cells, (nc,) * nd), axis=1)
         ix = (kji[:, ::-1] + 1).astype(np.int32)
         dds = dd[sel]
         # mg_box_lsf_stencil
-        all_d = np.ones((n3, 6))
+        all_d = np.ones((n3, 2 * nd))
         all_d[ix_cells] = dds
         dr2 = drs[q] * drs[q]
-        v = np.zeros((n3, 7))
-        for idim in range(3):
+        v = np.zeros((n3, 2 * nd + 1))
+        for idim in range(nd):
             lo, hi = all_d[:, 2 * idim], all_d[:, 2 * idim + 1]
             v[:, 1 + 2 * idim] = 1 / (0.5 * dr2[idim] * (lo + hi) * lo)
             v[:, 2 + 2 * idim] = 1 / (0.5 * dr2[idim] * (lo + hi) * hi)
         sm = v[:, 1]
-        for c in range(2, 7):  # -sum(v(2:)), left to right
+        for c in range(2, 2 * nd + 1):  # -sum(v(2:)), left to right
             sm = sm + v[:, c]
         v[:, 0] = -sm
         fb = np.zeros(n3)
-        for n in range(6):
+        for n in range(2 * nd):
             inside = all_d[:, n] < 1.0
             fb = np.where(inside, fb - v[:, n + 1], fb)
             v[inside, n + 1] = 0.0
-        shape = (nc, nc, nc)
-        out[q] = (v.reshape(shape + (7,)), (fb * boundary_value).reshape(shape), ix, dds)
+        shape = (nc,) * nd
+        out[q] = (v.reshape(shape + (2 * nd + 1,)), (fb * boundary_value).reshape(shape), ix,
+                  dds)
     return out

@@ -392,7 +392,8 @@ class Multigrid:
         """The electrode operator stencil of box `box_id` as afivo stores it
         (mg_box_lsf_stencil): v(7, nc, nc, nc) -- here an array of shape
         (nc, nc, nc, 7), [k][j][i][c] -- and bc_correction (nc, nc, nc) or
-        None; v = None removes it."""
+        None; v = None removes it. The 2-D library takes v (nc, nc, 5),
+        [j][i][c], and bc_correction (nc, nc)."""
         vp = None if v is None else np.ascontiguousarray(v, dtype=np.float64)
         bp = None if bc_correction is None else np.ascontiguousarray(
             bc_correction, dtype=np.float64)
@@ -403,11 +404,12 @@ class Multigrid:
     def set_box_lsf(self, box_id, ix, dd, bval, i_lsf):
         """Boundary distances of box `box_id` for mg_box_lpllsf_gradient:
         ix (n, 3) 1-based (i, j, k), dd (n, 6), bval (nc, nc, nc) the
-        electrode potential per cell; n = 0 removes."""
+        electrode potential per cell; n = 0 removes. The 2-D library takes
+        ix (n, 2), dd (n, 4), bval (nc, nc): NDIM is bval's rank."""
         ix = _i32(ix).reshape(-1)
         dd = np.ascontiguousarray(dd, dtype=np.float64).reshape(-1)
         bv = np.ascontiguousarray(bval, dtype=np.float64)
-        self.lib.call("mg_set_box_lsf", self.h, int(box_id), len(ix) // 3,
+        self.lib.call("mg_set_box_lsf", self.h, int(box_id), len(ix) // max(bv.ndim, 1),
                       ix.ctypes.data_as(capi.P_i32), dd.ctypes.data_as(capi.P_f64),
                       bv.ctypes.data_as(capi.P_f64), int(i_lsf))
 

@@ -52,6 +52,19 @@
 // k2_update_cyl (m_af_flux_schemes.f90:395-406), k2_box_sum_cyl (sum_2pr_box,
 // m_af_utils.f90:1008-1024) and the per-cell PFMG level-1 coefficients. They
 // are separate kernels: a Cartesian tree launches exactly what it did before.
+//
+// Electrodes (level-set boundaries on a Cartesian tree; afh_mg_set_box_stencil
+// / afh_mg_set_box_lsf): k2_gsrb_v, k2_residual_v, k2_rstr_fas_v,
+// k2_parent_rhs_v (stencil_gsrb_357 / stencil_apply_357, variable branch,
+// m_af_stencil.f90:433-441, 924-934, with bc_correction) on the lists of the
+// boxes that carry a stencil, k2_pair_box_v + k2_rhs_roundtrip (the fused
+// pair on levels with such boxes), the boxes' rows and bc_correction in the
+// PFMG level-1 solve, k2_lsf_gradient (mg_box_lpllsf_gradient,
+// m_af_multigrid.f90:2068-2087, and the norm of the corrected faces),
+// k2_electrode_bc (electrode_species_bc, src/streamer.f90:578-636),
+// k2_update_mask / k2_update_photo_mask + k2_mask_status (set_box_mask,
+// src/m_fluid.f90:469-483) and refine_electrode_dx in k2_refine_flags. Again
+// separate kernels: a tree without electrodes launches what it did before.
 #include <hip/hip_runtime.h>
 #include <float.h>
 #include <math.h>
@@ -575,12 +588,22 @@ __global__ void __launch_bounds__(64)
 // and index (entry NC: the low neighbour's cell NC, NC+1: the high
 // neighbour's cell 1; this box's r_min -+ NC dr can differ in the last bit).
 // A z-neighbour of the same level has this box's radii.
-template <int NC, int LPB, bool CYL>
+// rhs + bc_correction as half-sweep number np + 1 of a leg reads it (VAR)
+__device__ __forceinline__ double pair_rhs_in(double rv, const double *b, int cv, int np) {
+  if (!b) return rv;
+  const double bv = b[cv];
+  for (int q = 0; q < np; q++) rv = (rv + bv) - bv;
+  return rv + bv;
+}
+
+template <int NC, int LPB, bool CYL, bool VAR = false>
 __device__ __forceinline__ void
 pair_box_body(const double *__restrict__ src, double *__restrict__ dst,
               const double *__restrict__ rhs, const double *__restrict__ coarse,
               const afh_box_meta *__restrict__ meta, const int32_t *__restrict__ ids, int n,
-              int bsz, Coef2 cf, Bc4 g) {
+              int bsz, Coef2 cf, Bc4 g, const double *const *__restrict__ vp = nullptr,
+              const double *const *__restrict__ bp = nullptr, int pend = 0) {
+  static_assert(!(CYL && VAR), "electrode stencils on a cylindrical tree are not built");
   constexpr int NG = NC + 2, NB = NG * NG, NT = LPB, H = NC / 2, PW = 64 / LPB;
   __shared__ double P_[PW][NB];
   __shared__ double T_[CYL ? PW : 1][CYL ? 4 * (NC + 2) : 1];
@@ -605,15 +628,23 @@ pair_box_body(const double *__restrict__ src, double *__restrict__ dst,
   }
   const double *x = src + (size_t)(id - 1) * bsz, *r = rhs + (size_t)(id - 1) * bsz;
   double *y = dst + (size_t)(id - 1) * bsz;
+  // VAR: the box's own stencil and bc_correction (null: the level's cf)
+  const double *vb = VAR ? vp[id - 1] : nullptr, *bb = VAR ? bp[id - 1] : nullptr;
   for (int e = tid; e < NB; e += NT) P[e] = x[e];
   // B inputs: the odd ghost u < 2 NC (face u / H + 1, its odd positions) of
   // a same-level neighbour -- the neighbour's boundary cell, its four
-  // neighbours and rhs, loaded before A
+  // neighbours and rhs (VAR: and its stencil row), loaded before A
   constexpr int NGH = 2 * NC, GPT = (NGH + NT - 1) / NT;
   double bl[GPT][5];
+  double bv5[VAR ? GPT : 1][5];
+  bool bvar[VAR ? GPT : 1];
   for (int q = 0; q < GPT; q++) {
     const int u = tid + NT * q;
     for (int k = 0; k < 5; k++) bl[q][k] = 0.0;
+    if (VAR) {
+      for (int k = 0; k < 5; k++) bv5[q][k] = 0.0;
+      bvar[q] = false;
+    }
     if (u >= NGH) continue;
     const int nb = u / H + 1, d = (nb - 1) >> 1;
     const bool low = ((nb - 1) & 1) == 0;
@@ -629,6 +660,17 @@ pair_box_body(const double *__restrict__ src, double *__restrict__ dst,
       bl[q][2] = xs[c - NG];
       bl[q][3] = xs[c + NG];
       bl[q][4] = rhs[(size_t)(nid - 1) * bsz + c];
+      if (VAR) {
+        // the cell's index in the neighbour's v / bc_correction
+        const int i1n = low ? NC : 1;
+        const int cv = d == 0 ? (a - 1) * NC + (i1n - 1) : (i1n - 1) * NC + (a - 1);
+        bl[q][4] = pair_rhs_in(bl[q][4], bp[nid - 1], cv, pend);
+        const double *vn = vp[nid - 1];
+        if (vn) {
+          bvar[q] = true;
+          for (int k = 0; k < 5; k++) bv5[q][k] = vn[5 * (size_t)cv + k];
+        }
+      }
     }
   }
   __syncthreads();
@@ -636,7 +678,13 @@ pair_box_body(const double *__restrict__ src, double *__restrict__ dst,
   for (int q = tid; q < NC * H; q += NT) {
     const int j = q / H + 1, i = 2 - ((1 ^ j) & 1) + 2 * (q % H);
     const int c = ix2(NG, i, j);
-    if (CYL) {
+    if (VAR && vb) {
+      const int cv = (j - 1) * NC + (i - 1);
+      const double *v = vb + 5 * (size_t)cv;
+      P[c] = (pair_rhs_in(r[c], bb, cv, pend) - v[1] * P[c - 1] - v[2] * P[c + 1] -
+              v[3] * P[c - NG] - v[4] * P[c + NG]) /
+             v[0];
+    } else if (CYL) {
       const double *tc = T + 4 * (i - 1);
       P[c] = (r[c] - tc[1] * P[c - 1] - tc[2] * P[c + 1] - cf.c[3] * P[c - NG] -
               cf.c[4] * P[c + NG]) *
@@ -665,6 +713,10 @@ pair_box_body(const double *__restrict__ src, double *__restrict__ dst,
       v = (bl[q][4] - tc[1] * bl[q][0] - tc[2] * bl[q][1] - cf.c[3] * bl[q][2] -
            cf.c[4] * bl[q][3]) *
           tc[3];
+    } else if (VAR && nid > 0 && bvar[q]) {
+      v = (bl[q][4] - bv5[q][1] * bl[q][0] - bv5[q][2] * bl[q][1] - bv5[q][3] * bl[q][2] -
+           bv5[q][4] * bl[q][3]) /
+          bv5[q][0];
     } else if (nid > 0)
       v = (bl[q][4] - cf.c[1] * bl[q][0] - cf.c[2] * bl[q][1] - cf.c[3] * bl[q][2] -
            cf.c[4] * bl[q][3]) *
@@ -678,7 +730,13 @@ pair_box_body(const double *__restrict__ src, double *__restrict__ dst,
   for (int q = tid; q < NC * H; q += NT) {
     const int j = q / H + 1, i = 2 - ((0 ^ j) & 1) + 2 * (q % H);
     const int c = ix2(NG, i, j);
-    if (CYL) {
+    if (VAR && vb) {
+      const int cv = (j - 1) * NC + (i - 1);
+      const double *v = vb + 5 * (size_t)cv;
+      P[c] = (pair_rhs_in(r[c], bb, cv, pend + 1) - v[1] * P[c - 1] - v[2] * P[c + 1] -
+              v[3] * P[c - NG] - v[4] * P[c + NG]) /
+             v[0];
+    } else if (CYL) {
       const double *tc = T + 4 * (i - 1);
       P[c] = (r[c] - tc[1] * P[c - 1] - tc[2] * P[c + 1] - cf.c[3] * P[c - NG] -
               cf.c[4] * P[c + NG]) *
@@ -717,6 +775,30 @@ __global__ void __launch_bounds__(64)
                     const afh_box_meta *__restrict__ meta, const int32_t *__restrict__ ids,
                     int n, int bsz, Coef2 cf, Bc4 g) {
   pair_box_body<NC, LPB, true>(src, dst, rhs, coarse, meta, ids, n, bsz, cf, g);
+}
+
+// The pair once more for a level with electrode boxes: k2_pair_box_v is
+// pair_box_body<NC, LPB, false, VAR = true> (k2_pair_box above keeps its own
+// text, k2_pair_box_cyl its code: the VAR branches are compiled out of it;
+// levels without such boxes keep launching those). vp / bp: per box id the
+// variable stencil v(5, nc, nc) and bc_correction(nc, nc), or null. A box's
+// own cells take its stencil when it has one (k2_gsrb_v: divided by v(1)),
+// the recomputed boundary cell of a same-level neighbour takes the
+// neighbour's, every other cell cf (k2_gsrb: times inv_c1). The split
+// half-sweeps leave rhs = (rhs + b) - b after each one; here rhs is read
+// only, so half-sweep s of the leg forms the value the s - 1 earlier round
+// trips would have left (pend = those before phase A) and adds b;
+// k2_rhs_roundtrip stores the leg's round trips afterwards. Bitwise k2_gsrb +
+// k2_gsrb_v + k2_gc twice.
+template <int NC, int LPB = 64>
+__global__ void __launch_bounds__(64)
+    k2_pair_box_v(const double *__restrict__ src, double *__restrict__ dst,
+                  const double *__restrict__ rhs, const double *__restrict__ coarse,
+                  const afh_box_meta *__restrict__ meta, const int32_t *__restrict__ ids,
+                  int n, int bsz, Coef2 cf, Bc4 g, const double *const *__restrict__ vp,
+                  const double *const *__restrict__ bp, int pend) {
+  pair_box_body<NC, LPB, false, true>(src, dst, rhs, coarse, meta, ids, n, bsz, cf, g, vp, bp,
+                                      pend);
 }
 
 __device__ __forceinline__ double apply5(const double *p, int x, int ng, const Coef2 &cf) {
@@ -905,6 +987,200 @@ __global__ void __launch_bounds__(NT)
   if (copy) tmp[o + t] = phi[o + t];
 }
 
+// ------------------------------------------------------------ electrode boxes
+// Boxes the electrode surface crosses carry a variable 5-point stencil
+// (mg_box_lsf_stencil, m_af_multigrid.f90:1762-1834): v(5, nc, nc),
+// coefficients fastest as afivo stores them, and bc_correction(nc, nc) (f
+// times the electrode potential, mg_set_operators_lvl 1156-1160); vp / bp
+// index them by box id (bp null: no correction). These kernels run on the
+// lists of such boxes only, the constant kernels on the rest of each level:
+// a tree without electrodes launches none of them.
+__device__ __forceinline__ double apply5v(const double *p, int x, int ng, const double *v) {
+  return v[0] * p[x] + v[1] * p[x - 1] + v[2] * p[x + 1] + v[3] * p[x - ng] + v[4] * p[x + ng];
+}
+
+// stencil_gsrb_357, variable branch (m_af_stencil.f90:838-841, 924-934,
+// 975-978): rhs + bc_correction on every cell, the cells of the half sweep
+// divided by v(1), rhs - bc_correction; one thread per cell
+__global__ void __launch_bounds__(NT)
+    k2_gsrb_v(double *__restrict__ phi, double *__restrict__ rhs,
+              const int32_t *__restrict__ ids, int nc, int bsz,
+              const double *const *__restrict__ vp, const double *const *__restrict__ bp,
+              int redblack) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= nc * nc) return;
+  const int id = ids[blockIdx.y];
+  const int i = t % nc + 1, j = t / nc + 1, ng = nc + 2;
+  const size_t o = (size_t)(id - 1) * bsz;
+  double *p = phi + o, *r = rhs + o;
+  const int x = ix2(ng, i, j);
+  const double *v = vp[id - 1] + 5 * (size_t)t, *b = bp[id - 1];
+  double r1 = r[x];
+  if (b) r1 = r1 + b[t];
+  // i0 = 2 - iand(ieor(redblack, j), 1), i = i0, i0 + 2, ...
+  if (((i ^ (2 - ((redblack ^ j) & 1))) & 1) == 0)
+    p[x] = (r1 - v[1] * p[x - 1] - v[2] * p[x + 1] - v[3] * p[x - ng] - v[4] * p[x + ng]) /
+           v[0];
+  if (b) r[x] = r1 - b[t];
+}
+
+// The rhs round trips (rhs + bc_correction - bc_correction) of the n
+// half-sweeps a leg of fused variable pairs did (k2_pair_box_v), in the order
+// k2_gsrb_v applies them
+__global__ void __launch_bounds__(NT)
+    k2_rhs_roundtrip(double *__restrict__ rhs, const int32_t *__restrict__ ids, int nc, int bsz,
+                     const double *const *__restrict__ bp, int n) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= nc * nc) return;
+  const int id = ids[blockIdx.y];
+  const double *b = bp[id - 1];
+  if (!b) return;
+  double *r = rhs + (size_t)(id - 1) * bsz + ix2(nc + 2, t % nc + 1, t / nc + 1);
+  double v = *r;
+  for (int q = 0; q < n; q++) v = (v + b[t]) - b[t];
+  *r = v;
+}
+
+// residual_box with the variable stencil: tmp = rhs - (L phi - bc_correction)
+// (stencil_apply_357, m_af_stencil.f90:433-441, 472-475); with `red` the max
+// |tmp| is folded
+__global__ void __launch_bounds__(NT)
+    k2_residual_v(const double *__restrict__ phi, const double *__restrict__ rhs,
+                  double *__restrict__ tmp, const int32_t *__restrict__ ids, int nc, int bsz,
+                  const double *const *__restrict__ vp, const double *const *__restrict__ bp,
+                  unsigned long long *red) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  double mx = 0.0;
+  if (t < nc * nc) {
+    const int id = ids[blockIdx.y];
+    const int i = t % nc + 1, j = t / nc + 1, ng = nc + 2;
+    const size_t o = (size_t)(id - 1) * bsz;
+    const int x = ix2(ng, i, j);
+    double a = apply5v(phi + o, x, ng, vp[id - 1] + 5 * (size_t)t);
+    if (bp[id - 1]) a = a - bp[id - 1][t];
+    const double r = rhs[o + x] - a;
+    tmp[o + x] = r;
+    mx = fabs(r);
+  }
+  if (red) block_fold<true>(mx, red);
+}
+
+// k2_rstr_fas for children with a variable stencil
+__global__ void __launch_bounds__(NT)
+    k2_rstr_fas_v(double *__restrict__ phi, const double *__restrict__ rhs,
+                  double *__restrict__ tmp, const afh_box_meta *__restrict__ meta,
+                  const int32_t *__restrict__ ids, int nc, int bsz,
+                  const double *const *__restrict__ vp, const double *const *__restrict__ bp) {
+  const int hnc = nc >> 1;
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= hnc * hnc) return;
+  const int id = ids[blockIdx.y];
+  const afh_box_meta &m = meta[id - 1];
+  const int ii = t % hnc + 1, jj = t / hnc + 1, ng = nc + 2;
+  const int ic = ((m.ix[0] - 1) & 1) * hnc + ii, jc = ((m.ix[1] - 1) & 1) * hnc + jj;
+  const int i_f = 2 * ii - 1, j_f = 2 * jj - 1;
+  const size_t o = (size_t)(id - 1) * bsz, po = (size_t)(m.parent - 1) * bsz;
+  const double *p = phi + o, *r = rhs + o, *v = vp[id - 1], *b = bp[id - 1];
+  double res[4], ph[4];
+#pragma unroll
+  for (int q = 0; q < 4; q++) {
+    const int ci = i_f + (q & 1), cj = j_f + (q >> 1);
+    const int x = ix2(ng, ci, cj), cv = (cj - 1) * nc + (ci - 1);
+    double a = apply5v(p, x, ng, v + 5 * (size_t)cv);
+    if (b) a = a - b[cv];
+    res[q] = r[x] - a;
+    ph[q] = p[x];
+  }
+  tmp[po + ix2(ng, ic, jc)] = 0.25 * (res[0] + res[1] + res[2] + res[3]);
+  phi[po + ix2(ng, ic, jc)] = 0.25 * (ph[0] + ph[1] + ph[2] + ph[3]);
+}
+
+// k2_parent_rhs for parents with a variable stencil
+__global__ void __launch_bounds__(NT)
+    k2_parent_rhs_v(const double *__restrict__ phi, double *__restrict__ rhs,
+                    double *__restrict__ tmp, const int32_t *__restrict__ ids, int nc, int bsz,
+                    const double *const *__restrict__ vp, const double *const *__restrict__ bp,
+                    int copy) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  const int ng = nc + 2;
+  if (t >= ng * ng) return;
+  const int id = ids[blockIdx.y];
+  const size_t o = (size_t)(id - 1) * bsz;
+  const int i = t % ng, j = t / ng;
+  double r = rhs[o + t];
+  if (i >= 1 && i <= nc && j >= 1 && j <= nc) {
+    const int cv = (j - 1) * nc + (i - 1);
+    r = apply5v(phi + o, t, ng, vp[id - 1] + 5 * (size_t)cv);
+    if (bp[id - 1]) r = r - bp[id - 1][cv];
+  }
+  rhs[o + t] = r + tmp[o + t];
+  if (copy) tmp[o + t] = phi[o + t];
+}
+
+// mg_box_lpllsf_gradient, NDIM == 2 (m_af_multigrid.f90:2068-2087), on
+// electrode leaf boxes after k2_gradient: the faces next to the boundary from
+// the electrode potential. One thread per entry of the distance list; a face
+// two entries write (an entry's low face is its low neighbour cell's high
+// face) keeps the value of the later entry in the list, as the serial loop
+// leaves it -- each entry skips the faces a later entry rewrites (the entry
+// of each cell in LDS). Then mg_box_field_norm from the corrected faces
+// (2009-2014). One workgroup per box; nc <= 32.
+__global__ void __launch_bounds__(NT)
+    k2_lsf_gradient(const double *__restrict__ phi, const double *__restrict__ lsf,
+                    double *__restrict__ fc, double *__restrict__ norm,
+                    const int32_t *__restrict__ ids, const afh_box_meta *__restrict__ meta,
+                    int nc, int bsz, int fsz, const int *__restrict__ cnt,
+                    const int32_t *const *__restrict__ ixp,
+                    const double *const *__restrict__ ddp,
+                    const double *const *__restrict__ bvp, double fac) {
+  __shared__ int emap[32 * 32];
+  const int id = ids[blockIdx.x];
+  const int n = cnt[id - 1], ng = nc + 2, nf = nc + 1;
+  for (int c = threadIdx.x; c < nc * nc; c += blockDim.x) emap[c] = -1;
+  __syncthreads();
+  const int32_t *X = ixp[id - 1];
+  for (int e = threadIdx.x; e < n; e += blockDim.x)
+    atomicMax(&emap[(X[2 * e + 1] - 1) * nc + (X[2 * e] - 1)], e);
+  __syncthreads();
+  const double *p = phi + (size_t)(id - 1) * bsz, *l = lsf + (size_t)(id - 1) * bsz;
+  double *f = fc + (size_t)(id - 1) * fsz;
+  const double *D = ddp[id - 1], *bv = bvp[id - 1];
+  const double ix_ = fac / meta[id - 1].dr[0], iy = fac / meta[id - 1].dr[1];
+  auto fx = [&](int d, int a, int b) { return d * nf * nf + (b - 1) * nf + (a - 1); };
+  for (int e = threadIdx.x; e < n; e += blockDim.x) {
+    const int i = X[2 * e], j = X[2 * e + 1];
+    const int ce = (j - 1) * nc + (i - 1);
+    if (emap[ce] > e) continue;  // a later entry of the same cell
+    const int c = ix2(ng, i, j);
+    if (l[c] < 0) continue;
+    const double *dd = D + 4 * e;
+    const double pc = p[c], bc = bv[ce];
+    // the face of direction q is also written by the entry of the cell
+    // across it (direction q ^ 1) if that entry is later and writes it
+    auto later = [&](int q) {
+      const int d = q >> 1, sgn = (q & 1) ? 1 : -1;
+      int a[2] = {i, j};
+      a[d] += sgn;
+      if (a[d] < 1 || a[d] > nc) return false;
+      const int e2 = emap[(a[1] - 1) * nc + (a[0] - 1)];
+      return e2 > e && !(l[ix2(ng, a[0], a[1])] < 0) && D[4 * e2 + (q ^ 1)] < 1;
+    };
+    if (dd[0] < 1 && !later(0)) f[fx(0, i, j)] = ix_ * (pc - bc) / dd[0];
+    if (dd[1] < 1 && !later(1)) f[fx(0, i + 1, j)] = ix_ * (bc - pc) / dd[1];
+    if (dd[2] < 1 && !later(2)) f[fx(1, i, j)] = iy * (pc - bc) / dd[2];
+    if (dd[3] < 1 && !later(3)) f[fx(1, i, j + 1)] = iy * (bc - pc) / dd[3];
+  }
+  if (!norm) return;
+  __threadfence_block();
+  __syncthreads();  // the workgroup's face writes above are visible after it
+  for (int t = threadIdx.x; t < nc * nc; t += blockDim.x) {
+    const int i = t % nc + 1, j = t / nc + 1;
+    const double sx = f[fx(0, i, j)] + f[fx(0, i + 1, j)];
+    const double sy = f[fx(1, i, j)] + f[fx(1, i, j + 1)];
+    norm[(size_t)(id - 1) * bsz + ix2(ng, i, j)] = 0.5 * sqrt(sx * sx + sy * sy);
+  }
+}
+
 // whole-block copies (DTIMES(:)): mode 0 dst = a - b (correct_children's
 // tmp = phi - tmp), 1 dst = a, 2 dst = 0
 __global__ void __launch_bounds__(NT)
@@ -1042,14 +1318,16 @@ __global__ void __launch_bounds__(1024)
 // AFH_COARSE_PFMG: the reference's HYPRE StructPFMG restated
 // (afh_pfmg_dev.h), the NDIM = 2 grid: gather rhs + boundary terms (the
 // folded operator's coefficients, b2r per face) and phi, solve, scatter;
-// the vectors and the wave levels' operators in LDS
+// the vectors and the wave levels' operators in LDS. vbc: per box id the
+// bc_correction of an electrode box (null: none; a null table: no such box)
 __global__ void __launch_bounds__(1024)
     k2_cs_pfmg(const afh_pf::PfLvl *__restrict__ Lg, int nl, int wave_from,
                const double *__restrict__ A, const double *__restrict__ Pw,
                const double *__restrict__ b2r, const uint8_t *__restrict__ fmask,
                double *__restrict__ phi, const double *__restrict__ rhs,
                const afh_box_meta *__restrict__ meta, const int32_t *__restrict__ ids, int nid,
-               int nc, int bsz, Bc4 g, double tol, int max_iter, int *__restrict__ iters_out) {
+               int nc, int bsz, Bc4 g, double tol, int max_iter, int *__restrict__ iters_out,
+               const double *const *__restrict__ vbc) {
   extern __shared__ double pf_sm[];
   __shared__ double slot;
   const afh_pf::PfLvl L0 = Lg[0];
@@ -1070,6 +1348,8 @@ __global__ void __launch_bounds__(1024)
     const int fm = fmask[p];
     for (int nb = 0; nb < 4; nb++)
       if ((fm >> nb) & 1) rv = rv + b2r[(size_t)nb * L0.np + p] * g.bc[nb].value;
+    // an electrode box: + bc_correction (coarse_solver_set_rhs_phi's level-set term)
+    if (vbc && vbc[id - 1]) rv = rv + vbc[id - 1][t];
     b[p] = rv;
     X0[p] = phi[c];
   }
@@ -1479,11 +1759,24 @@ struct PhotoArgs {
   int s;
 };
 
-template <int NS, bool CYL, bool PHOTO = false>
+// MASK (k2_update_mask, k2_update_photo_mask; afh_fluid_set_update_mask):
+// set_box_mask's electrode part (src/m_fluid.f90:469-483). A cell whose level
+// set M.lsf is <= 0 keeps the weighted sum of the previous states: no
+// chemistry source, no photoionization, no flux divergence
+// (m_af_flux_schemes.f90:408-416 with the mask); a box with no other cell
+// (M.stat[id - 1] = 0, k2_mask_status) adds no chemistry limit either
+// (add_source_terms returns before it, m_fluid.f90:332).
+struct MaskArgs {
+  const double *lsf;
+  const uint8_t *stat;
+};
+
+template <int NS, bool CYL, bool PHOTO = false, bool MASK = false>
 __device__ __forceinline__ void
 update_body(UpdArgs A, const int32_t *__restrict__ ids,
             const afh_box_meta *__restrict__ meta, int nc, int bsz, int fsz,
-            unsigned long long *red, PhotoArgs P = PhotoArgs{nullptr, 0}) {
+            unsigned long long *red, PhotoArgs P = PhotoArgs{nullptr, 0},
+            MaskArgs M = MaskArgs{nullptr, nullptr}) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   double cmin = 1e100;
   const int ns = NS == MAXS ? A.ns : NS;
@@ -1491,6 +1784,9 @@ update_body(UpdArgs A, const int32_t *__restrict__ ids,
     const int id = ids[blockIdx.y];
     const int i = t % nc + 1, j = t / nc + 1, ng = nc + 2, nf = nc + 1;
     const size_t x = (size_t)(id - 1) * bsz + ix2(ng, i, j);
+    // `where (lsf <= 0) mask = .false.` (a NaN stays true)
+    const bool upd = !MASK || !(M.lsf[x] <= 0.0);
+    const bool src = !MASK || M.stat[id - 1] != 0;
     double y[NS], dens[NS], der[NS];
 #pragma unroll
     for (int s = 0; s < ns; s++) {
@@ -1512,7 +1808,7 @@ update_body(UpdArgs A, const int32_t *__restrict__ ids,
       for (int q = 0; q < R.n_out; q++)
         der[R.ix_out[q] - 1] = der[R.ix_out[q] - 1] + rate * R.mult_out[q];
     }
-    if (A.last_step) {
+    if (A.last_step && src) {
       const double eps = 1e-100;
 #pragma unroll
       for (int s = 0; s < ns; s++) {
@@ -1528,18 +1824,22 @@ update_body(UpdArgs A, const int32_t *__restrict__ ids,
         cmin = fmin(cmin, a / b);
       }
     }
-    if (PHOTO) {
+    if (PHOTO && upd) {
       const double pho = P.photo[x];
       der[A.e_index] = der[A.e_index] + pho;
       der[P.s] = der[P.s] + pho;
     }
+    if (upd) {
 #pragma unroll
-    for (int s = 0; s < ns; s++) y[s] = y[s] + A.dt * der[s];
+      for (int s = 0; s < ns; s++) y[s] = y[s] + A.dt * der[s];
+    }
     const double *F = A.F + (size_t)(id - 1) * fsz;
     const int f0 = (j - 1) * nf + (i - 1), d2 = nf * nf;
     const double dtx = A.dt / meta[id - 1].dr[0], dty = A.dt / meta[id - 1].dr[1];
     const int e = A.e_index;
-    if (CYL) {
+    if (MASK && !upd) {
+      // (no flux divergence)
+    } else if (CYL) {
       double rf1, rf2;
       cyl_flux_factors(meta[id - 1].r_min[0], meta[id - 1].dr[0], i, rf1, rf2);
       y[e] = y[e] + dtx * (rf1 * F[f0] - rf2 * F[f0 + 1]) +
@@ -1575,6 +1875,76 @@ __global__ void __launch_bounds__(NT)
                         const afh_box_meta *__restrict__ meta, int nc, int bsz, int fsz,
                         unsigned long long *red, PhotoArgs P) {
   update_body<NS, true, true>(A, ids, meta, nc, bsz, fsz, red, P);
+}
+
+template <int NS>
+__global__ void __launch_bounds__(NT)
+    k2_update_mask(UpdArgs A, const int32_t *__restrict__ ids,
+                   const afh_box_meta *__restrict__ meta, int nc, int bsz, int fsz,
+                   unsigned long long *red, MaskArgs M) {
+  update_body<NS, false, false, true>(A, ids, meta, nc, bsz, fsz, red, PhotoArgs{nullptr, 0}, M);
+}
+
+template <int NS>
+__global__ void __launch_bounds__(NT)
+    k2_update_photo_mask(UpdArgs A, const int32_t *__restrict__ ids,
+                         const afh_box_meta *__restrict__ meta, int nc, int bsz, int fsz,
+                         unsigned long long *red, PhotoArgs P, MaskArgs M) {
+  update_body<NS, false, true, true>(A, ids, meta, nc, bsz, fsz, red, P, M);
+}
+
+// per leaf box whether set_box_mask leaves any cell to update (any(mask));
+// one workgroup per box
+__global__ void __launch_bounds__(64)
+    k2_mask_status(const double *__restrict__ lsf, const int32_t *__restrict__ ids, int nc,
+                   int bsz, uint8_t *__restrict__ stat) {
+  const int id = ids[blockIdx.x];
+  int any = 0;
+  for (int t = threadIdx.x; t < nc * nc; t += blockDim.x)
+    if (!(lsf[(size_t)(id - 1) * bsz + ix2(nc + 2, t % nc + 1, t / nc + 1)] <= 0.0)) any = 1;
+  any = __any(any);
+  if (threadIdx.x == 0) stat[id - 1] = any ? 1 : 0;
+}
+
+// electrode_species_bc, NDIM == 2 (src/streamer.f90:578-636): one thread per
+// interior cell of an electrode box. A cell with lsf < 0 is written only by
+// its own thread and its electron density is read only by cells with lsf < 0
+// next to it -- which never use it (they average neighbours with lsf > 0) --
+// so the in-place update is race-free and order-independent, as in the
+// reference.
+struct ElecBcArgs {
+  double *sp[MAXS];
+  int ns;
+  const double *lsf;
+  double *ne, *ion;
+  int neumann_zero;
+};
+
+__global__ void __launch_bounds__(NT)
+    k2_electrode_bc(ElecBcArgs A, const int32_t *__restrict__ ids, int nc, int bsz) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= nc * nc) return;
+  const int ng = nc + 2;
+  const size_t b0 = (size_t)(ids[blockIdx.y] - 1) * bsz;
+  const int c = ix2(ng, t % nc + 1, t / nc + 1);
+  const double *lsf = A.lsf + b0;
+  if (!(lsf[c] < 0)) return;
+  for (int s = 0; s < A.ns; s++) A.sp[s][b0 + c] = 0.0;
+  if (!A.neumann_zero) return;
+  const int nb[4] = {c - 1, c + 1, c - ng, c + ng};
+  int cnt = 0;
+  double sum = 0.0;  // sum(dens_nb, mask=(lsf_nb > 0)), in array order
+#pragma unroll
+  for (int m = 0; m < 4; m++)
+    if (lsf[nb[m]] > 0) {
+      cnt++;
+      sum = sum + A.ne[b0 + nb[m]];
+    }
+  if (cnt > 0) {
+    const double v = sum / cnt;
+    A.ne[b0 + c] = v;
+    A.ion[b0 + c] = v;
+  }
 }
 
 // photoionization_rate_from_alpha (src/m_photoi.f90:232-270) with a constant
@@ -1775,6 +2145,25 @@ struct afh_mg {
   double *d_pf_A = nullptr, *d_pf_P = nullptr, *d_pf_b2r = nullptr;
   uint8_t *d_pf_fmask = nullptr;
   int *d_pf_iters = nullptr;
+  // electrode boxes (afh_mg_set_box_stencil / afh_mg_set_box_lsf): device
+  // arrays per box id (null: none), their device pointer tables, and the
+  // level lists split into constant- and variable-stencil boxes
+  // (prepare_var). Without such boxes any_var / any_lsf stay false and every
+  // launch is the one of a tree without electrodes.
+  std::vector<double *> h_vp, h_bp, h_dd, h_bv;
+  std::vector<int32_t *> h_ix;
+  std::vector<int> h_lsf_n;
+  double **d_vp = nullptr, **d_bp = nullptr, **d_dd = nullptr, **d_bv = nullptr;
+  int32_t **d_ix = nullptr;
+  int *d_lsf_n = nullptr;
+  int i_lsf = 0;
+  bool var_dirty = false, any_var = false, any_lsf = false;
+  std::vector<uint8_t> lvl_var;  // per level: it has variable-stencil boxes
+  LevelList ids_c, ids_v, leaves_c, leaves_v, parents_c, parents_v, lsf_leaves;
+  // host copies of the level-1 boxes' stencils for the PFMG setup, and its
+  // generation (the setup is rebuilt when a level-1 stencil changes)
+  std::map<int, std::vector<double>> h_vl1;
+  uint64_t v1_gen = 0, pf_v1_gen = 0;
 };
 
 struct afh_fluid {
@@ -1783,6 +2172,12 @@ struct afh_fluid {
   double *d_td = nullptr, *d_chem = nullptr;
   DevReaction *d_reac = nullptr;
   // (k2_update is compiled for the species count, 1..12)
+  int32_t *d_ids = nullptr;  // box list of afh_electrode_species_bc
+  int ids_cap = 0;
+  // afh_fluid_set_update_mask: the level set whose cells <= 0 the update
+  // leaves alone (0: none); per box id whether any cell is updated
+  int mask_iv = 0;
+  uint8_t *d_mstat = nullptr;
 };
 
 namespace afh2 {
@@ -2239,6 +2634,10 @@ int32_t afh_mg_create(afh_tree *t, const afh_mg_desc *d, afh_mg **out) {
   mg->pair = mg->pair && (t->nc == 4 || t->nc == 8 || t->nc == 16) &&
              d->n_cycle_down % 2 == 0 && d->n_cycle_up % 2 == 0;
   if (mg->pair) H2(hipMalloc(&mg->alt, sizeof(double) * (size_t)t->nb * t->bsz));
+  mg->h_vp.assign(t->nb, nullptr), mg->h_bp.assign(t->nb, nullptr);
+  mg->h_dd.assign(t->nb, nullptr), mg->h_bv.assign(t->nb, nullptr);
+  mg->h_ix.assign(t->nb, nullptr), mg->h_lsf_n.assign(t->nb, 0);
+  mg->lvl_var.assign(t->nlvl, 0);
   *out = mg;
   return AFH_OK;
 }
@@ -2251,6 +2650,15 @@ int32_t afh_mg_destroy(afh_mg *mg) {
   hipFree(mg->d_lvl_c);
   hipFree(mg->d_pf_lvl), hipFree(mg->d_pf_A), hipFree(mg->d_pf_P), hipFree(mg->d_pf_b2r);
   hipFree(mg->d_pf_fmask), hipFree(mg->d_pf_iters);
+  for (size_t q = 0; q < mg->h_vp.size(); q++) {
+    hipFree(mg->h_vp[q]), hipFree(mg->h_bp[q]), hipFree(mg->h_dd[q]), hipFree(mg->h_bv[q]);
+    hipFree(mg->h_ix[q]);
+  }
+  hipFree(mg->d_vp), hipFree(mg->d_bp), hipFree(mg->d_dd), hipFree(mg->d_bv);
+  hipFree(mg->d_ix), hipFree(mg->d_lsf_n);
+  for (LevelList *L : {&mg->ids_c, &mg->ids_v, &mg->leaves_c, &mg->leaves_v, &mg->parents_c,
+                       &mg->parents_v, &mg->lsf_leaves})
+    free_list(*L);
   for (auto &g : mg->graphs)
     if (g.second.exec) hipGraphExecDestroy(g.second.exec);
   delete mg;
@@ -2260,6 +2668,64 @@ int32_t afh_mg_destroy(afh_mg *mg) {
 }  // extern "C"
 
 namespace afh2 {
+
+// Device tables and split level lists after afh_mg_set_box_stencil /
+// afh_mg_set_box_lsf changed them; the captured V-cycles are dropped (their
+// launches hold the old lists)
+static int32_t prepare_var(afh_mg *mg) {
+  if (!mg->var_dirty) return AFH_OK;
+  afh_tree *t = mg->t;
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  H2(hipStreamIsCapturing(t->stream, &cs));
+  if (cs != hipStreamCaptureStatusNone)
+    return set_error(AFH_ERR_STATE, "electrode stencils changed during a graph capture");
+  mg->var_dirty = false;
+  H2(hipStreamSynchronize(t->stream));
+  for (auto &g : mg->graphs)
+    if (g.second.exec) hipGraphExecDestroy(g.second.exec);
+  mg->graphs.clear();
+  const int nb = t->nb, nl = t->nlvl;
+  auto table = [&](auto **d, const auto &h) -> int32_t {
+    if (!*d) H2(hipMalloc(d, sizeof(h[0]) * nb));
+    H2(hipMemcpy(*d, h.data(), sizeof(h[0]) * nb, hipMemcpyHostToDevice));
+    return AFH_OK;
+  };
+  int32_t e;
+  if ((e = table(&mg->d_vp, mg->h_vp)) || (e = table(&mg->d_bp, mg->h_bp)) ||
+      (e = table(&mg->d_dd, mg->h_dd)) || (e = table(&mg->d_bv, mg->h_bv)) ||
+      (e = table(&mg->d_ix, mg->h_ix)) || (e = table(&mg->d_lsf_n, mg->h_lsf_n)))
+    return e;
+  mg->any_var = mg->any_lsf = false;
+  mg->lvl_var.assign(nl, 0);
+  for (int q = 0; q < nb; q++) {
+    if (mg->h_vp[q]) mg->any_var = true, mg->lvl_var[t->boxes[q].lvl - 1] = 1;
+    if (mg->h_lsf_n[q]) mg->any_lsf = true;
+  }
+  auto split = [&](const std::vector<std::vector<int32_t>> &src, LevelList &c,
+                   LevelList &v) -> int32_t {
+    std::vector<std::vector<int32_t>> lc(nl), lv(nl);
+    for (int l = 0; l < nl; l++)
+      for (int32_t id : src[l]) (mg->h_vp[id - 1] ? lv : lc)[l].push_back(id);
+    int32_t e2;
+    if ((e2 = upload_list(c, lc)) || (e2 = upload_list(v, lv))) return e2;
+    return AFH_OK;
+  };
+  if ((e = split(t->h_ids, mg->ids_c, mg->ids_v)) ||
+      (e = split(t->h_leaves, mg->leaves_c, mg->leaves_v)) ||
+      (e = split(t->h_parents, mg->parents_c, mg->parents_v)))
+    return e;
+  std::vector<std::vector<int32_t>> ll(nl);
+  for (int l = 0; l < nl; l++)
+    for (int32_t id : t->h_leaves[l])
+      if (mg->h_lsf_n[id - 1]) ll[l].push_back(id);
+  return upload_list(mg->lsf_leaves, ll);
+}
+
+// the constant-stencil part of a level list (the whole list without
+// electrode boxes)
+static const LevelList &cst(const afh_mg *mg, const LevelList &all, const LevelList &c) {
+  return mg->any_var ? c : all;
+}
 
 // the folded 1-D operator h tridiag(1, -2, 1) with end diagonals -h
 // (Neumann) / -3h (Dirichlet): cosine / sine eigenbasis (same as the 3-D
@@ -2293,6 +2759,7 @@ static int32_t solve_coarse_pfmg(afh_mg *mg) {
   const size_t n0 = (size_t)nx * ny;
   bool fresh = !mg->d_pf_lvl;
   for (int q = 0; q < 4; q++) fresh = fresh || mg->pf_bc[q] != M.bc[q].type;
+  fresh = fresh || mg->pf_v1_gen != mg->v1_gen;  // a level-1 stencil changed
   if (fresh) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     H2(hipStreamIsCapturing(t->stream, &cs));
@@ -2304,12 +2771,17 @@ static int32_t solve_coarse_pfmg(afh_mg *mg) {
     for (int q = 0; q < nid; q++) {
       const int id = t->h_ids[0][q];
       const afh_box_meta &m = t->boxes[id - 1];
+      // an electrode box: its own rows (mg_box_lsf_stencil), before the
+      // physical boundaries are folded in
+      auto it = mg->h_vl1.find(id);
+      const double *vst = it == mg->h_vl1.end() ? nullptr : it->second.data();
       for (int j = 1; j <= nc; j++)
         for (int i = 1; i <= nc; i++) {
           const int gi[2] = {(m.ix[0] - 1) * nc + i, (m.ix[1] - 1) * nc + j};
           const size_t g = (size_t)(gi[1] - 1) * nx + (gi[0] - 1);
           double c[7] = {mg->lvl_c[0].c[0], mg->lvl_c[0].c[1], mg->lvl_c[0].c[2],
                          mg->lvl_c[0].c[3], mg->lvl_c[0].c[4], 0.0, 0.0};
+          if (vst) memcpy(c, vst + 5 * ((size_t)(j - 1) * nc + (i - 1)), 5 * sizeof(double));
           if (t->cyl()) {
             // af_stencil_get_box's cylindrical coefficients of the cell
             // (m_af_stencil.f90:1056-1066), before the boundaries are folded
@@ -2381,6 +2853,7 @@ static int32_t solve_coarse_pfmg(afh_mg *mg) {
       }
     }
     for (int q = 0; q < 4; q++) mg->pf_bc[q] = M.bc[q].type;
+    mg->pf_v1_gen = mg->v1_gen;
   }
   const int nt = std::min(1024, std::max(256, (int)((n0 + 63) / 64 * 64)));
   prof_mark(t, AFH_PROF_CS);
@@ -2388,7 +2861,8 @@ static int32_t solve_coarse_pfmg(afh_mg *mg) {
                      mg->pf_nl, mg->pf_wave, mg->d_pf_A, mg->d_pf_P, mg->d_pf_b2r, mg->d_pf_fmask,
                      t->ccv(mg->d.i_phi), t->ccv(mg->d.i_rhs), t->d_boxes, t->ids.at(1), nid,
                      t->nc, t->bsz, t->bc4(mg->d.i_phi), mg->d.coarse_tol, mg->d.coarse_cycles,
-                     mg->d_pf_iters);
+                     mg->d_pf_iters,
+                     mg->any_var && mg->lvl_var[0] ? (const double *const *)mg->d_bp : nullptr);
   H2_LAUNCH("k2_cs_pfmg");
   prof_end(t, AFH_PROF_CS, 0.0);
   return gc_lvl(t, 1, mg->d.i_phi, true);
@@ -2433,7 +2907,44 @@ static int32_t gsrb_boxes(afh_mg *mg, int lvl, bool up, bool skip_corners = fals
   afh_tree *t = mg->t;
   const int n = t->ids.n(lvl);
   const int nc_ = up ? mg->d.n_cycle_up : mg->d.n_cycle_down;
-  if (mg->pair && n) {
+  // a level with electrode boxes: the pair's variable form, or the split
+  // half-sweeps (AFH_PAIR2D=0)
+  const bool var = mg->any_var && mg->lvl_var[lvl - 1];
+  if (mg->pair && n && var) {
+    double *phi = t->ccv(mg->d.i_phi);
+    const double *rh = t->ccv(mg->d.i_rhs);
+    const int32_t *ids = t->ids.at(lvl);
+    const Coef2 cf = mg->lvl_c[lvl - 1];
+    const Bc4 g = t->bc4(mg->d.i_phi);
+    for (int p = 0; p < nc_; p++) {
+      const double *src = (p & 1) ? mg->alt : phi;
+      double *dst = (p & 1) ? phi : mg->alt;
+      if (t->nc == 4)
+        hipLaunchKernelGGL((k2_pair_box_v<4, 16>), dim3((n + 3) / 4), dim3(64), 0, t->stream,
+                           src, dst, rh, phi, t->d_boxes, ids, n, t->bsz, cf, g, mg->d_vp,
+                           mg->d_bp, 2 * p);
+      else if (t->nc == 8)
+        hipLaunchKernelGGL((k2_pair_box_v<8, 32>), dim3((n + 1) / 2), dim3(64), 0, t->stream,
+                           src, dst, rh, phi, t->d_boxes, ids, n, t->bsz, cf, g, mg->d_vp,
+                           mg->d_bp, 2 * p);
+      else
+        hipLaunchKernelGGL(k2_pair_box_v<16>, dim3(n), dim3(64), 0, t->stream, src, dst, rh,
+                           phi, t->d_boxes, ids, n, t->bsz, cf, g, mg->d_vp, mg->d_bp, 2 * p);
+      H2_LAUNCH("k2_pair_box_v");
+    }
+    const int nv = mg->ids_v.n(lvl);
+    hipLaunchKernelGGL(k2_rhs_roundtrip, grid2(t->nc * t->nc, nv), blk2(t->nc * t->nc), 0,
+                       t->stream, t->ccv(mg->d.i_rhs), mg->ids_v.at(lvl), t->nc, t->bsz,
+                       mg->d_bp, 2 * nc_);
+    H2_LAUNCH("k2_rhs_roundtrip");
+    if (up && !skip_corners) {
+      hipLaunchKernelGGL(k2_corners, dim3((4 * n + NT - 1) / NT), dim3(NT), 0, t->stream,
+                         phi, t->d_boxes, t->ids.at(lvl), n, t->nc, t->bsz);
+      H2_LAUNCH("k2_corners");
+    }
+    return AFH_OK;
+  }
+  if (mg->pair && n && !var) {
     // n_cycle fused pairs, phi -> alt -> phi (n_cycle even); the corners of
     // the up leg's last fill after them
     double *phi = t->ccv(mg->d.i_phi);
@@ -2477,6 +2988,24 @@ static int32_t gsrb_boxes(afh_mg *mg, int lvl, bool up, bool skip_corners = fals
     }
     return AFH_OK;
   }
+  if (var) {
+    // the constant kernel on the level's ordinary boxes, k2_gsrb_v on the rest
+    const int ncst = mg->ids_c.n(lvl), nv = mg->ids_v.n(lvl);
+    for (int s = 1; s <= 2 * nc_; s++) {
+      if (ncst) {
+        hipLaunchKernelGGL(k2_gsrb, grid2(t->nc * t->nc / 2, ncst), blk2(t->nc * t->nc / 2), 0,
+                           t->stream, t->ccv(mg->d.i_phi), t->ccv(mg->d.i_rhs),
+                           mg->ids_c.at(lvl), t->nc, t->bsz, mg->lvl_c[lvl - 1], s);
+        H2_LAUNCH("k2_gsrb");
+      }
+      hipLaunchKernelGGL(k2_gsrb_v, grid2(t->nc * t->nc, nv), blk2(t->nc * t->nc), 0, t->stream,
+                         t->ccv(mg->d.i_phi), t->ccv(mg->d.i_rhs), mg->ids_v.at(lvl), t->nc,
+                         t->bsz, mg->d_vp, mg->d_bp, s);
+      H2_LAUNCH("k2_gsrb_v");
+      if (int32_t e = gc_lvl(t, lvl, mg->d.i_phi, up && s == 2 * nc_)) return e;
+    }
+    return AFH_OK;
+  }
   for (int s = 1; s <= 2 * nc_; s++) {
     if (n) {
       // timed on levels of >= 256 boxes, as libafivo_hip's pair: the small
@@ -2499,6 +3028,27 @@ static int32_t gsrb_boxes(afh_mg *mg, int lvl, bool up, bool skip_corners = fals
   return AFH_OK;
 }
 
+// k2_parent_rhs over the parents of level lvl (a Cartesian tree): the
+// constant kernel on the ordinary boxes, k2_parent_rhs_v on electrode boxes
+static int32_t parent_rhs(afh_mg *mg, int lvl, int copy) {
+  afh_tree *t = mg->t;
+  const LevelList &L = cst(mg, t->parents, mg->parents_c);
+  const int ncst = L.n(lvl), nv = mg->any_var ? mg->parents_v.n(lvl) : 0;
+  if (ncst) {
+    hipLaunchKernelGGL(k2_parent_rhs, grid2(t->bsz, ncst), blk2(t->bsz), 0, t->stream,
+                       t->ccv(mg->d.i_phi), t->ccv(mg->d.i_rhs), t->ccv(mg->d.i_tmp),
+                       L.at(lvl), t->nc, t->bsz, mg->lvl_c[lvl - 1], copy);
+    H2_LAUNCH("k2_parent_rhs");
+  }
+  if (nv) {
+    hipLaunchKernelGGL(k2_parent_rhs_v, grid2(t->bsz, nv), blk2(t->bsz), 0, t->stream,
+                       t->ccv(mg->d.i_phi), t->ccv(mg->d.i_rhs), t->ccv(mg->d.i_tmp),
+                       mg->parents_v.at(lvl), t->nc, t->bsz, mg->d_vp, mg->d_bp, copy);
+    H2_LAUNCH("k2_parent_rhs_v");
+  }
+  return AFH_OK;
+}
+
 // update_coarse (691-738)
 static int32_t update_coarse(afh_mg *mg, int lvl) {
   afh_tree *t = mg->t;
@@ -2510,10 +3060,22 @@ static int32_t update_coarse(afh_mg *mg, int lvl) {
                        mg->lvl_c[lvl - 1]);
     H2_LAUNCH("k2_rstr_fas_cyl");
   } else if (n) {
-    hipLaunchKernelGGL(k2_rstr_fas, grid2(t->nc * t->nc / 4, n), blk2(t->nc * t->nc / 4), 0, t->stream,
-                       t->ccv(mg->d.i_phi), t->ccv(mg->d.i_rhs), t->ccv(mg->d.i_tmp),
-                       t->d_boxes, t->ids.at(lvl), t->nc, t->bsz, mg->lvl_c[lvl - 1]);
-    H2_LAUNCH("k2_rstr_fas");
+    const LevelList &L = cst(mg, t->ids, mg->ids_c);
+    const int ncst = L.n(lvl), nv = mg->any_var ? mg->ids_v.n(lvl) : 0;
+    if (ncst) {
+      hipLaunchKernelGGL(k2_rstr_fas, grid2(t->nc * t->nc / 4, ncst),
+                         blk2(t->nc * t->nc / 4), 0, t->stream, t->ccv(mg->d.i_phi),
+                         t->ccv(mg->d.i_rhs), t->ccv(mg->d.i_tmp), t->d_boxes, L.at(lvl), t->nc,
+                         t->bsz, mg->lvl_c[lvl - 1]);
+      H2_LAUNCH("k2_rstr_fas");
+    }
+    if (nv) {
+      hipLaunchKernelGGL(k2_rstr_fas_v, grid2(t->nc * t->nc / 4, nv), blk2(t->nc * t->nc / 4),
+                         0, t->stream, t->ccv(mg->d.i_phi), t->ccv(mg->d.i_rhs),
+                         t->ccv(mg->d.i_tmp), t->d_boxes, mg->ids_v.at(lvl), t->nc, t->bsz,
+                         mg->d_vp, mg->d_bp);
+      H2_LAUNCH("k2_rstr_fas_v");
+    }
   }
   if (int32_t e = gc_lvl(t, lvl - 1, mg->d.i_phi, true)) return e;
   const int np = t->parents.n(lvl - 1);
@@ -2523,10 +3085,7 @@ static int32_t update_coarse(afh_mg *mg, int lvl) {
                        t->parents.at(lvl - 1), t->nc, t->bsz, mg->lvl_c[lvl - 2], 1);
     H2_LAUNCH("k2_parent_rhs_cyl");
   } else if (np) {
-    hipLaunchKernelGGL(k2_parent_rhs, grid2(t->bsz, np), blk2(t->bsz), 0, t->stream,
-                       t->ccv(mg->d.i_phi), t->ccv(mg->d.i_rhs), t->ccv(mg->d.i_tmp),
-                       t->parents.at(lvl - 1), t->nc, t->bsz, mg->lvl_c[lvl - 2], 1);
-    H2_LAUNCH("k2_parent_rhs");
+    if (int32_t e = parent_rhs(mg, lvl - 1, 1)) return e;
   }
   return AFH_OK;
 }
@@ -2553,8 +3112,36 @@ static int32_t correct_children(afh_mg *mg, int lvl, bool corners = false) {
   return AFH_OK;
 }
 
-static int32_t residual_lvl(afh_mg *mg, int lvl, const LevelList &L, bool fold) {
+// the variable-stencil part of level list L (one of the tree's ids / leaves
+// / parents) and its constant part; v = null without electrode boxes
+static const LevelList &split_of(const afh_mg *mg, const LevelList &L, const LevelList **v) {
+  const afh_tree *t = mg->t;
+  *v = nullptr;
+  if (!mg->any_var) return L;
+  if (&L == &t->leaves) return *v = &mg->leaves_v, mg->leaves_c;
+  if (&L == &t->parents) return *v = &mg->parents_v, mg->parents_c;
+  return *v = &mg->ids_v, mg->ids_c;
+}
+
+// k2_residual_v on boxes [l0, l1] of the variable list V
+static int32_t residual_var(afh_mg *mg, const LevelList &V, int l0, int l1, bool fold) {
   afh_tree *t = mg->t;
+  const int n = V.off[l1] - V.off[l0 - 1];
+  if (!n) return AFH_OK;
+  hipLaunchKernelGGL(k2_residual_v, grid2(t->nc * t->nc, n), blk2(t->nc * t->nc), 0, t->stream,
+                     t->ccv(mg->d.i_phi), t->ccv(mg->d.i_rhs), t->ccv(mg->d.i_tmp), V.at(l0),
+                     t->nc, t->bsz, mg->d_vp, mg->d_bp,
+                     fold ? t->red + 3 * RED_SHARDS : nullptr);
+  H2_LAUNCH("k2_residual_v");
+  return AFH_OK;
+}
+
+static int32_t residual_lvl(afh_mg *mg, int lvl, const LevelList &L_, bool fold) {
+  afh_tree *t = mg->t;
+  const LevelList *V;
+  const LevelList &L = split_of(mg, L_, &V);
+  if (V)
+    if (int32_t e = residual_var(mg, *V, lvl, lvl, fold)) return e;
   const int n = L.n(lvl);
   if (!n) return AFH_OK;
   if (t->cyl())
@@ -2573,10 +3160,16 @@ static int32_t residual_lvl(afh_mg *mg, int lvl, const LevelList &L, bool fold) 
 
 // the residual of levels 1 .. max_lvl of list L in one launch (each box's
 // coefficients by its level; false: max_lvl boxes exceed the grid's y limit)
-static bool residual_all(afh_mg *mg, int max_lvl, const LevelList &L, bool fold) {
+// (err: a launch error of the variable boxes' part; the list then counts as
+// done and the caller returns the error)
+static bool residual_all(afh_mg *mg, int max_lvl, const LevelList &L_, bool fold,
+                         int32_t &err) {
   afh_tree *t = mg->t;
+  if (!mg->all_lvl || L_.off[max_lvl] - L_.off[0] > 65535) return false;
+  const LevelList *V;
+  const LevelList &L = split_of(mg, L_, &V);
+  if (V && (err = residual_var(mg, *V, 1, max_lvl, fold))) return true;
   const int n = L.off[max_lvl] - L.off[0];
-  if (!mg->all_lvl || n > 65535) return false;
   if (n && t->cyl())
     hipLaunchKernelGGL(k2_residual_cyl, grid2(t->nc * t->nc, n), blk2(t->nc * t->nc), cyl_lds(t),
                        t->stream, t->ccv(mg->d.i_phi), t->ccv(mg->d.i_rhs), t->ccv(mg->d.i_tmp),
@@ -2611,10 +3204,11 @@ static int32_t vcycle(afh_mg *mg, bool set_residual, int max_lvl, bool max_out) 
   if (!set_residual) return AFH_OK;
   afh_tree *t = mg->t;
   if (max_out && (e = red_init(t, 3, 0.0))) return e;
-  if (max_out ? residual_all(mg, max_lvl, t->leaves, true) &&
-                    residual_all(mg, max_lvl, t->parents, false)
-              : residual_all(mg, max_lvl, t->ids, false))
-    return AFH_OK;
+  int32_t re = AFH_OK;
+  if (max_out ? residual_all(mg, max_lvl, t->leaves, true, re) &&
+                    (re || residual_all(mg, max_lvl, t->parents, false, re))
+              : residual_all(mg, max_lvl, t->ids, false, re))
+    return re;
   for (int l = 1; l <= max_lvl; l++) {
     if (max_out) {
       // leaves fold, parents do not (the same tmp values)
@@ -2632,6 +3226,9 @@ static int32_t vcycle(afh_mg *mg, bool set_residual, int max_lvl, bool max_out) 
 // (not while kernels are being timed: the events are host calls)
 static int32_t vcycle_run(afh_mg *mg, bool set_residual, int max_lvl, bool max_out) {
   afh_tree *t = mg->t;
+  // a changed electrode stencil drops the captured graphs: this call runs
+  // eagerly and the next one captures again
+  if (int32_t e = prepare_var(mg)) return e;
   if (!mg->use_graphs || t->prof_class) return vcycle(mg, set_residual, max_lvl, max_out);
   const int key = (max_lvl << 2) | (set_residual ? 2 : 0) | (max_out ? 1 : 0);
   afh_mg::Graph &g = mg->graphs[key];
@@ -2692,6 +3289,7 @@ int32_t afh_mg_fas_fmg(afh_mg *mg, int32_t set_residual, int32_t have_guess) {
   double *phi = t->ccv(mg->d.i_phi), *rhs = t->ccv(mg->d.i_rhs), *tmp = t->ccv(mg->d.i_tmp);
   const int nc = t->nc;
   int32_t e;
+  if ((e = prepare_var(mg))) return e;
   if (have_guess) {
     for (int l = t->nlvl; l >= 2; l--) {
       // set_coarse_phi_rhs (742-776)
@@ -2712,9 +3310,7 @@ int32_t afh_mg_fas_fmg(afh_mg *mg, int32_t set_residual, int32_t have_guess) {
                            mg->lvl_c[l - 2], 0);
         H2_LAUNCH("k2_parent_rhs_cyl");
       } else if (np) {
-        hipLaunchKernelGGL(k2_parent_rhs, grid2(t->bsz, np), blk2(t->bsz), 0, t->stream, phi, rhs,
-                           tmp, t->parents.at(l - 1), nc, t->bsz, mg->lvl_c[l - 2], 0);
-        H2_LAUNCH("k2_parent_rhs");
+        if ((e = parent_rhs(mg, l - 1, 0))) return e;
       }
     }
   } else {
@@ -2753,6 +3349,20 @@ int32_t afh_mg_compute_phi_gradient(afh_mg *mg, int32_t i_fc, double fac, int32_
   afh_tree *t = mg->t;
   if (i_fc < 1 || i_fc > t->nvf || i_norm < 0 || i_norm > t->nvc)
     return set_error(AFH_ERR_ARG, "bad variable index");
+  if (int32_t e = prepare_var(mg)) return e;
+  // electrode leaf boxes: mg_box_lpllsf_gradient after the ordinary
+  // gradient, then their |E| again from the corrected faces (the leaves of
+  // every level in one launch)
+  auto lsf_part = [&]() -> int32_t {
+    const int n = mg->any_lsf ? mg->lsf_leaves.off[t->nlvl] - mg->lsf_leaves.off[0] : 0;
+    if (!n) return AFH_OK;
+    hipLaunchKernelGGL(k2_lsf_gradient, dim3(n), dim3(blk2n(t->nc * t->nc)), 0, t->stream,
+                       t->ccv(mg->d.i_phi), t->ccv(mg->i_lsf), t->fcv(i_fc),
+                       i_norm ? t->ccv(i_norm) : nullptr, mg->lsf_leaves.at(1), t->d_boxes,
+                       t->nc, t->bsz, t->fsz, mg->d_lsf_n, mg->d_ix, mg->d_dd, mg->d_bv, fac);
+    H2_LAUNCH("k2_lsf_gradient");
+    return AFH_OK;
+  };
   // every level in one launch (the box's spacing comes from its meta)
   const int n_all = t->ids.off[t->nlvl] - t->ids.off[0];
   if (mg->all_lvl && n_all <= 65535) {
@@ -2763,7 +3373,7 @@ int32_t afh_mg_compute_phi_gradient(afh_mg *mg, int32_t i_fc, double fac, int32_
                          t->bsz, t->fsz, fac);
       H2_LAUNCH("k2_gradient");
     }
-    return AFH_OK;
+    return lsf_part();
   }
   for (int l = 1; l <= t->nlvl; l++) {
     const int n = t->ids.n(l);
@@ -2774,6 +3384,87 @@ int32_t afh_mg_compute_phi_gradient(afh_mg *mg, int32_t i_fc, double fac, int32_
                        t->bsz, t->fsz, fac);
     H2_LAUNCH("k2_gradient");
   }
+  return lsf_part();
+}
+
+// The electrode entry points, as afivo_hip.h with the 2-D shapes
+// (afivo_hip_2d.h): v(5, nc, nc), bc_correction(nc, nc); ix(2, n), dd(4, n),
+// bval(nc, nc)
+int32_t afh_mg_set_box_stencil(afh_mg *mg, int32_t id, const double *v,
+                               const double *bc_correction) {
+  if (!mg) return set_error(AFH_ERR_ARG, "null mg");
+  afh_tree *t = mg->t;
+  if (id < 1 || id > t->nb) return set_error(AFH_ERR_ARG, "bad box id %d", id);
+  if (t->boxes[id - 1].lvl < 1 || t->boxes[id - 1].lvl > t->nlvl)
+    return set_error(AFH_ERR_ARG, "box %d is not in use", id);
+  if (t->cyl())
+    return set_error(AFH_ERR_UNSUPPORTED,
+                     "2-D: electrode stencils in cylindrical coordinates are not built");
+  const bool l1 = t->boxes[id - 1].lvl == 1;
+  if (v && l1 && mg->d.coarse_mode == AFH_COARSE_DIRECT)
+    return set_error(AFH_ERR_UNSUPPORTED,
+                     "2-D: AFH_COARSE_DIRECT's basis does not diagonalise a level-1 grid "
+                     "with electrode stencils; use AFH_COARSE_PFMG");
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  H2(hipStreamIsCapturing(t->stream, &cs));
+  if (cs != hipStreamCaptureStatusNone)
+    return set_error(AFH_ERR_STATE, "afh_mg_set_box_stencil during a graph capture");
+  const size_t n2 = (size_t)t->nc * t->nc;
+  H2(hipStreamSynchronize(t->stream));
+  hipFree(mg->h_vp[id - 1]), hipFree(mg->h_bp[id - 1]);
+  mg->h_vp[id - 1] = mg->h_bp[id - 1] = nullptr;
+  mg->var_dirty = true;
+  if (l1) {  // the level-1 solve's host copy
+    mg->v1_gen++;
+    if (v) mg->h_vl1[id].assign(v, v + 5 * n2);
+    else mg->h_vl1.erase(id);
+  }
+  if (!v) return AFH_OK;
+  H2(hipMalloc(&mg->h_vp[id - 1], sizeof(double) * 5 * n2));
+  H2(hipMemcpy(mg->h_vp[id - 1], v, sizeof(double) * 5 * n2, hipMemcpyHostToDevice));
+  if (bc_correction) {
+    H2(hipMalloc(&mg->h_bp[id - 1], sizeof(double) * n2));
+    H2(hipMemcpy(mg->h_bp[id - 1], bc_correction, sizeof(double) * n2, hipMemcpyHostToDevice));
+  }
+  return AFH_OK;
+}
+
+int32_t afh_mg_set_box_lsf(afh_mg *mg, int32_t id, int32_t n, const int32_t *ix,
+                           const double *dd, const double *bval, int32_t i_lsf) {
+  if (!mg) return set_error(AFH_ERR_ARG, "null mg");
+  afh_tree *t = mg->t;
+  if (id < 1 || id > t->nb || n < 0) return set_error(AFH_ERR_ARG, "bad box id / count");
+  if (t->boxes[id - 1].lvl < 1 || t->boxes[id - 1].lvl > t->nlvl)
+    return set_error(AFH_ERR_ARG, "box %d is not in use", id);
+  if (t->cyl())
+    return set_error(AFH_ERR_UNSUPPORTED,
+                     "2-D: level sets in cylindrical coordinates are not built");
+  if (n > 0) {
+    if (!ix || !dd || !bval || i_lsf < 1 || i_lsf > t->nvc)
+      return set_error(AFH_ERR_ARG, "afh_mg_set_box_lsf: bad argument");
+    if (t->nc > 32) return set_error(AFH_ERR_UNSUPPORTED, "2-D level sets: box size %d", t->nc);
+    for (int q = 0; q < 2 * n; q++)
+      if (ix[q] < 1 || ix[q] > t->nc) return set_error(AFH_ERR_ARG, "cell index out of box");
+  }
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  H2(hipStreamIsCapturing(t->stream, &cs));
+  if (cs != hipStreamCaptureStatusNone)
+    return set_error(AFH_ERR_STATE, "afh_mg_set_box_lsf during a graph capture");
+  const size_t n2 = (size_t)t->nc * t->nc;
+  H2(hipStreamSynchronize(t->stream));
+  hipFree(mg->h_ix[id - 1]), hipFree(mg->h_dd[id - 1]), hipFree(mg->h_bv[id - 1]);
+  mg->h_ix[id - 1] = nullptr, mg->h_dd[id - 1] = mg->h_bv[id - 1] = nullptr;
+  mg->h_lsf_n[id - 1] = 0;
+  mg->var_dirty = true;
+  if (n == 0) return AFH_OK;
+  H2(hipMalloc(&mg->h_ix[id - 1], sizeof(int32_t) * 2 * n));
+  H2(hipMemcpy(mg->h_ix[id - 1], ix, sizeof(int32_t) * 2 * n, hipMemcpyHostToDevice));
+  H2(hipMalloc(&mg->h_dd[id - 1], sizeof(double) * 4 * n));
+  H2(hipMemcpy(mg->h_dd[id - 1], dd, sizeof(double) * 4 * n, hipMemcpyHostToDevice));
+  H2(hipMalloc(&mg->h_bv[id - 1], sizeof(double) * n2));
+  H2(hipMemcpy(mg->h_bv[id - 1], bval, sizeof(double) * n2, hipMemcpyHostToDevice));
+  mg->h_lsf_n[id - 1] = n;
+  mg->i_lsf = i_lsf;
   return AFH_OK;
 }
 
@@ -2827,6 +3518,7 @@ int32_t afh_fluid_destroy(afh_fluid *f) {
   if (!f) return AFH_OK;
   hipStreamSynchronize(f->t->stream);
   hipFree(f->d_td), hipFree(f->d_chem), hipFree(f->d_reac);
+  hipFree(f->d_ids), hipFree(f->d_mstat);
   delete f;
   return AFH_OK;
 }
@@ -2960,6 +3652,21 @@ static int32_t update(afh_fluid *f, double dt, int32_t s_deriv, int32_t n_prev,
   A.dt = dt, A.dt_chemistry_nmin = f->d.dt_chemistry_nmin;
   if (A.last_step)
     if (int32_t e = red_init(t, 2, 1e100)) return e;
+  MaskArgs M{nullptr, nullptr};
+  if (f->mask_iv > 0) {
+    if (t->cyl())
+      return set_error(AFH_ERR_UNSUPPORTED,
+                       "2-D: the update mask in cylindrical coordinates is not built");
+    // the leaves' mask summary from the level set as it is now
+    if (!f->d_mstat) H2(hipMalloc(&f->d_mstat, (size_t)t->nb));
+    M.lsf = t->ccv(f->mask_iv), M.stat = f->d_mstat;
+    const int nl = t->leaves.off[t->nlvl] - t->leaves.off[0];
+    for (int c0 = 0; c0 < nl; c0 += 65535) {
+      hipLaunchKernelGGL(k2_mask_status, dim3(std::min(65535, nl - c0)), dim3(64), 0, t->stream,
+                         M.lsf, t->leaves.at(1) + c0, t->nc, t->bsz, f->d_mstat);
+      H2_LAUNCH("k2_mask_status");
+    }
+  }
   for (int l = 1; l <= t->nlvl; l++) {
     const int n = t->leaves.n(l);
     if (!n) continue;
@@ -2967,7 +3674,27 @@ static int32_t update(afh_fluid *f, double dt, int32_t s_deriv, int32_t n_prev,
     const dim3 bk = blk2(t->nc * t->nc);
     const int32_t *ids = t->leaves.at(l);
     unsigned long long *red = t->red + 2 * RED_SHARDS;
-    if (f->d.i_photo > 0) {
+    if (M.lsf) {
+      // the sibling kernels with set_box_mask (and the photoionization term)
+      const PhotoArgs P{f->d.i_photo > 0 ? t->ccv(f->d.i_photo) : nullptr,
+                        f->d.photo_species - 1};
+      const bool photo = f->d.i_photo > 0;
+      switch (A.ns) {
+#define AFH2_UPD(N)                                                                         \
+  case N:                                                                                   \
+    if (photo)                                                                              \
+      hipLaunchKernelGGL(k2_update_photo_mask<N>, g, bk, 0, t->stream, A, ids, t->d_boxes,  \
+                         t->nc, t->bsz, t->fsz, red, P, M);                                 \
+    else                                                                                    \
+      hipLaunchKernelGGL(k2_update_mask<N>, g, bk, 0, t->stream, A, ids, t->d_boxes, t->nc, \
+                         t->bsz, t->fsz, red, M);                                           \
+    break;
+        AFH2_UPD(1) AFH2_UPD(2) AFH2_UPD(3) AFH2_UPD(4) AFH2_UPD(5) AFH2_UPD(6) AFH2_UPD(7)
+        AFH2_UPD(8) AFH2_UPD(9) AFH2_UPD(10) AFH2_UPD(11) AFH2_UPD(12)
+      default: AFH2_UPD(MAXS)
+#undef AFH2_UPD
+      }
+    } else if (f->d.i_photo > 0) {
       // the sibling kernels with the photoionization term
       const PhotoArgs P{t->ccv(f->d.i_photo), f->d.photo_species - 1};
       const bool cyl = t->cyl();
@@ -3027,6 +3754,48 @@ int32_t afh_field_set_rhs(afh_fluid *f, int32_t i_rhs, int32_t s_in) {
 int32_t afh_field_set_rhs_maxabs(afh_fluid *f, int32_t i_rhs, int32_t s_in, double *max_rhs) {
   if (!f || !max_rhs) return set_error(AFH_ERR_ARG, "afh_field_set_rhs_maxabs: null");
   return set_rhs(f, i_rhs, s_in, max_rhs);
+}
+
+int32_t afh_electrode_species_bc(afh_fluid *f, int32_t i_lsf, int32_t i_1pos_ion,
+                                 int32_t neumann_zero, int32_t n_ids, const int32_t *ids) {
+  if (!f) return set_error(AFH_ERR_ARG, "afh_electrode_species_bc: null");
+  afh_tree *t = f->t;
+  if (i_lsf < 1 || i_lsf > t->nvc || i_1pos_ion < 1 || i_1pos_ion > t->nvc || n_ids < 0 ||
+      (n_ids && !ids))
+    return set_error(AFH_ERR_ARG, "electrode_species_bc: bad argument");
+  for (int q = 0; q < n_ids; q++)
+    if (ids[q] < 1 || ids[q] > t->nb) return set_error(AFH_ERR_ARG, "bad box id");
+  if (!n_ids) return AFH_OK;
+  if (n_ids > 65535) return set_error(AFH_ERR_UNSUPPORTED, "electrode_species_bc: %d boxes", n_ids);
+  if (n_ids > f->ids_cap) {
+    // the previous list may still be read by a queued launch
+    H2(hipStreamSynchronize(t->stream));
+    hipFree(f->d_ids);
+    f->d_ids = nullptr;
+    f->ids_cap = 0;
+    H2(hipMalloc(&f->d_ids, sizeof(int32_t) * n_ids));
+    f->ids_cap = n_ids;
+  }
+  // pageable source: the copy is staged before the call returns
+  H2(hipMemcpyAsync(f->d_ids, ids, sizeof(int32_t) * n_ids, hipMemcpyHostToDevice, t->stream));
+  ElecBcArgs A;
+  A.ns = f->d.n_species;
+  for (int s = 0; s < A.ns; s++) A.sp[s] = t->ccv(f->d.species_iv[s]);
+  A.lsf = t->ccv(i_lsf);
+  A.ne = t->ccv(f->d.i_electron);
+  A.ion = t->ccv(i_1pos_ion);
+  A.neumann_zero = neumann_zero ? 1 : 0;
+  hipLaunchKernelGGL(k2_electrode_bc, grid2(t->nc * t->nc, n_ids), blk2(t->nc * t->nc), 0,
+                     t->stream, A, f->d_ids, t->nc, t->bsz);
+  H2_LAUNCH("k2_electrode_bc");
+  return AFH_OK;
+}
+
+int32_t afh_fluid_set_update_mask(afh_fluid *f, int32_t i_lsf) {
+  if (!f) return set_error(AFH_ERR_ARG, "afh_fluid_set_update_mask: null");
+  if (i_lsf < 0 || i_lsf > f->t->nvc) return set_error(AFH_ERR_ARG, "bad i_lsf");
+  f->mask_iv = i_lsf;
+  return AFH_OK;
 }
 
 int32_t afh_flux_upwind_tree(afh_fluid *f, int32_t s_deriv, double *dt_lim) {
@@ -3264,6 +4033,7 @@ struct RefineArgs2 {
   DevLT td;
   double N;
   const double *ne, *E;
+  const uint8_t *elec;  // per box id: tagged mg_lsf_box, or null
 };
 
 // default_refinement (src/m_refine.f90:198-298), NDIM = 2, per cell, reduced
@@ -3285,6 +4055,7 @@ __global__ void __launch_bounds__(NT)
   const double min_dx = b.dr[0] < b.dr[1] ? b.dr[0] : b.dr[1];
   const double max_dx = b.dr[0] > b.dr[1] ? b.dr[0] : b.dr[1];
   const int bw = p.buffer_width;
+  const int elec = A.elec ? A.elec[id - 1] : 0;
   double rmin[2], rmax[2];
   for (int d = 0; d < 2; d++) rmin[d] = b.r_min[d], rmax[d] = b.r_min[d] + b.dr[d] * nc;
   int any_do = 0, any_keep = 0;
@@ -3315,6 +4086,8 @@ __global__ void __launch_bounds__(NT)
       if (dist - p.seed_width[n] < 2 * max_dx && max_dx > p.init_fac * p.seed_width[n])
         f = AFH_DO_REF;
     }
+    // refine_electrode_dx on the boxes of the electrode (m_refine.f90:255-259)
+    if (elec && max_dx > p.electrode_dx) f = AFH_DO_REF;
     for (int n = 0; n < p.n_regions; n++) {
       bool in = max_dx > p.region_dr[n];
       for (int d = 0; d < 2; d++)
@@ -3573,7 +4346,6 @@ int32_t afh_refine_flags(afh_fluid *f, const afh_refine_desc *d, const uint8_t *
                          int32_t *flags, uint32_t *masks) {
   if (!f || !d || !flags || !masks) return set_error(AFH_ERR_ARG, "afh_refine_flags: null");
   afh_tree *t = f->t;
-  if (electrode_box) return set_error(AFH_ERR_UNSUPPORTED, "2-D: electrodes");
   if (d->n_seeds > AFH_MAX_REFINE_REGIONS || d->n_regions > AFH_MAX_REFINE_REGIONS ||
       d->n_limits > AFH_MAX_REFINE_REGIONS || d->buffer_width < 0 ||
       d->buffer_width > t->nc || d->i_electron < 1 || d->i_electron > t->nvc ||
@@ -3587,7 +4359,13 @@ int32_t afh_refine_flags(afh_fluid *f, const afh_refine_desc *d, const uint8_t *
   H2(hipMalloc(&d_masks, sizeof(uint32_t) * nb));
   H2(hipMemsetAsync(d_flags, 0, sizeof(int32_t) * nb, t->stream));
   H2(hipMemsetAsync(d_masks, 0, sizeof(uint32_t) * nb, t->stream));
+  uint8_t *d_elec = nullptr;
+  if (electrode_box) {
+    H2(hipMalloc(&d_elec, nb));
+    H2(hipMemcpyAsync(d_elec, electrode_box, nb, hipMemcpyHostToDevice, t->stream));
+  }
   RefineArgs2 A;
+  A.elec = d_elec;
   A.d = *d;
   A.td = dev_lt(f->d.td, f->d_td);
   A.N = f->d.gas_number_density;
@@ -3601,7 +4379,7 @@ int32_t afh_refine_flags(afh_fluid *f, const afh_refine_desc *d, const uint8_t *
   H2(hipMemcpyAsync(flags, d_flags, sizeof(int32_t) * nb, hipMemcpyDeviceToHost, t->stream));
   H2(hipMemcpyAsync(masks, d_masks, sizeof(uint32_t) * nb, hipMemcpyDeviceToHost, t->stream));
   H2(hipStreamSynchronize(t->stream));
-  hipFree(d_flags), hipFree(d_masks);
+  hipFree(d_flags), hipFree(d_masks), hipFree(d_elec);
   return AFH_OK;
 }
 

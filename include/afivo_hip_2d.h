@@ -18,7 +18,12 @@
  *   - bc arrays of afh_set_cc_methods: bc[0..3]; afh_set_bc: nb = 1..4;
  *   - host arrays of afh_cc_put/get hold, per box, box%cc(0:nc+1, 0:nc+1, iv)
  *     (i fastest), boxes in id order; afh_fc_put/get box%fc(1:nc+1, 1:nc+1,
- *     1:2, ivf).
+ *     1:2, ivf);
+ *   - electrode boxes: afh_mg_set_box_stencil's v is box%stencils(ix)%v(5, nc,
+ *     nc), coefficients fastest, in the order (i,j), (i-1,j), (i+1,j),
+ *     (i,j-1), (i,j+1), bc_correction (nc, nc) or NULL; afh_mg_set_box_lsf's
+ *     ix is (2, n), 1-based (i, j), dd (4, n) in the same neighbour order,
+ *     bval (nc, nc).
  *
  * Built: the tree with its ghost cells (af_gc_box with neighbour copy,
  * bc_to_gc, af_gc_interp / af_gc_interp_lim / mg_sides_rb, corners),
@@ -32,10 +37,16 @@
  * tree with afh_tree_set_coord, afivo_hip_2d_cyl.h), and Helmholtz
  * photoionization with the Zheleznyak source (afh_photoi_set_src,
  * afh_photoi_helmh_compute, the i_photo term of the species step; the source
- * needs a constant gas density). Not built in 2-D
- * (AFH_ERR_UNSUPPORTED or not exported): electrodes / level sets, variable
+ * needs a constant gas density), and electrodes on Cartesian trees (level-set
+ * boundaries on the field multigrid: the variable stencils of the boxes the
+ * surface crosses in the smoother, residual, FAS restriction and the PFMG
+ * level-1 solve, mg_box_lpllsf_gradient, electrode_species_bc, set_box_mask
+ * and refine_electrode_dx; below). Not built in 2-D
+ * (AFH_ERR_UNSUPPORTED or not exported): electrodes in cylindrical
+ * coordinates, variable
  * gas density, the temperature rate forms, sharding, ion
- * secondary emission, AFH_COARSE_DIRECT on a cylindrical tree. Built in
+ * secondary emission, AFH_COARSE_DIRECT on a cylindrical tree or with a
+ * level-1 electrode stencil. Built in
  * round 4 for the 2-D time loop (afh.driver over this library,
  * programs/standard_2d/tests/test_2d_rtest.log): the device regrid with the
  * prolongation of the automatic variables, default_refinement's flags, the
@@ -93,7 +104,8 @@ int32_t afh_flux_update_densities(afh_fluid *f, double dt, int32_t s_deriv, int3
 int32_t afh_set_cc_prolong(afh_tree *t, int32_t iv, int32_t method, int32_t limiter);
 int32_t afh_tree_regrid(afh_tree *old, const afh_tree_desc *desc, afh_tree **out);
 /* default_refinement reduced per box; masks use the 2-D bit (dj+1)*3 + (di+1);
- * the seeds' / regions' first two coordinates; electrode_box must be NULL */
+ * the seeds' / regions' first two coordinates; electrode_box: per box 1 when
+ * the box is tagged mg_lsf_box (refine_electrode_dx / electrode_dx), or NULL */
 int32_t afh_refine_flags(afh_fluid *f, const afh_refine_desc *d,
                          const uint8_t *electrode_box, int32_t *flags,
                          uint32_t *masks);
@@ -132,6 +144,37 @@ int32_t afh_photoi_set_src(afh_fluid *f, int32_t i_rhs, int32_t alpha_col, doubl
 int32_t afh_photoi_helmh_compute(afh_mg *const *modes, int32_t n_modes,
                                  const double *coeffs, int32_t i_photo,
                                  double max_rel_res, int32_t max_fmg, int32_t *n_fmg);
+
+/* Electrodes (level-set boundaries), as afivo_hip.h with the 2-D shapes
+ * above, on Cartesian trees (an AFH_COORD_CYL tree: AFH_ERR_UNSUPPORTED).
+ * Errors: AFH_ERR_ARG for an id outside 1 .. n_boxes, a box not in use, a
+ * cell index outside the box or a missing array; AFH_ERR_STATE during a graph
+ * capture; AFH_ERR_UNSUPPORTED for a stencil on a level-1 box of an
+ * AFH_COARSE_DIRECT multigrid (use AFH_COARSE_PFMG: the level-1 rows of such
+ * boxes are the box's v before the physical boundaries are folded in, its
+ * bc_correction is added to the gathered rhs, and the set-up is rebuilt when
+ * a level-1 stencil changes). Setting or removing a stencil or a distance
+ * list drops the multigrid's captured hipGraphs: the next V-cycle runs
+ * eagerly and captures again. Levels with variable boxes smooth with the
+ * fused pair's variable form (k2_pair_box_v; AFH_PAIR2D=0: split
+ * half-sweeps, k2_gsrb + k2_gsrb_v), bitwise the same;
+ * levels and trees without them launch what they launched before.
+ * afh_mg_compute_phi_gradient corrects the faces of the leaf boxes with a
+ * distance list (mg_box_lpllsf_gradient) and forms their |E| from the
+ * corrected faces. */
+int32_t afh_mg_set_box_stencil(afh_mg *mg, int32_t id, const double *v,
+                               const double *bc_correction);
+int32_t afh_mg_set_box_lsf(afh_mg *mg, int32_t id, int32_t n, const int32_t *ix,
+                           const double *dd, const double *bval, int32_t i_lsf);
+/* electrode_species_bc, NDIM == 2 (src/streamer.f90:578-636) over boxes ids */
+int32_t afh_electrode_species_bc(afh_fluid *f, int32_t i_lsf, int32_t i_1pos_ion,
+                                 int32_t neumann_zero, int32_t n_ids,
+                                 const int32_t *ids);
+/* set_box_mask (src/m_fluid.f90:469-483) for the species update, with or
+ * without the photoionization term: a cell with cc(i_lsf) <= 0 keeps the
+ * weighted previous states (no chemistry, no photoionization, no flux
+ * divergence), a leaf with no other cell adds no chemistry limit; 0: off */
+int32_t afh_fluid_set_update_mask(afh_fluid *f, int32_t i_lsf);
 
 #ifdef __cplusplus
 }
