@@ -65,6 +65,13 @@
 // k2_update_mask / k2_update_photo_mask + k2_mask_status (set_box_mask,
 // src/m_fluid.f90:469-483) and refine_electrode_dx in k2_refine_flags. Again
 // separate kernels: a tree without electrodes launches what it did before.
+//
+// Mobile ions (afh_fluid_desc.n_ions > 0; src/m_fluid.f90:198-208): k2_gc2 per
+// flux species into the fluid's own second ghost layers, k2_flux_ions (the
+// fluxes of every flux species of a level in one launch, the per-face
+// conductivity sum in registers), k2_consistent[_cyl] per flux variable and
+// k2_update_ions (update_body with the ions' divergences). A fluid without
+// ions launches what it did before.
 #include <hip/hip_runtime.h>
 #include <float.h>
 #include <math.h>
@@ -1583,6 +1590,114 @@ __global__ void __launch_bounds__(NT)
   block_fold<true>(smax, red + RED_SHARDS);
 }
 
+// Mobile ions (input_data%mobile_ions; afh_fluid_desc.n_ions > 0): the flux
+// species are the electrons and then the ions in descriptor order
+// (m_fluid.f90:198-205). n[q] the density of ion q at the derivative state,
+// F[q] its face flux, mu[q] = mobility * N_inv (as the host multiplies it,
+// the reference's `mobilities(n) * N_inv`), q[q] its charge sign; gc2 holds
+// 1 + n planes of nb * 4 * nc doubles (plane 0 the electrons', gstride
+// doubles apart).
+struct IonFluxArgs {
+  int n;
+  const double *dens[AFH_MAX_IONS];
+  double *F[AFH_MAX_IONS];
+  double mu[AFH_MAX_IONS];
+  double q[AFH_MAX_IONS];
+  size_t gstride;
+};
+
+// k2_flux once more for a fluid with mobile ions (k2_flux keeps its own
+// text): per face the field, the two table lookups and N_inv once, then every
+// ion's Koren-limited upwind value (upwind where q E_f > 0, flux_direction),
+// its flux (q mu E_f) u and its term of the face's conductivity
+// sigma = mu_e u_e + sum_n mu_n u_n, which stays in registers; the maximum of
+// that sum is folded, the CFL sum is the electrons' alone. NI: the ion count
+// when it is a compile-time case (1, 6), 0 for any count (I.n).
+template <int NI>
+__global__ void __launch_bounds__(NT)
+    k2_flux_ions(FluxArgs A, IonFluxArgs I, const int32_t *__restrict__ ids,
+                 const afh_box_meta *__restrict__ meta, int nc, int bsz, int fsz,
+                 unsigned long long *red) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  double cfl = -HUGE_VAL, smax = -HUGE_VAL;
+  const int ni = NI ? NI : I.n;
+  if (t < nc * nc) {
+    const int id = ids[blockIdx.y];
+    const int i = t % nc + 1, j = t / nc + 1, ng = nc + 2, nf = nc + 1;
+    const size_t o = (size_t)(id - 1) * bsz, of = (size_t)(id - 1) * fsz;
+    const size_t og = (size_t)(id - 1) * 4 * nc;
+    const double *ne = A.ne + o, *E = A.E + o;
+    const double *Ef = A.Ef + of;
+    double *F = A.F + of;
+    const double *g2 = A.gc2 + og;
+    const double idx[2] = {1 / meta[id - 1].dr[0], 1 / meta[id - 1].dr[1]};
+    const int c0 = ix2(ng, i, j);
+    const int cc[2] = {i, j}, st[2] = {1, ng};
+    const int other[2] = {j, i};
+    const int face[2] = {(j - 1) * nf + (i - 1), nf * nf + (j - 1) * nf + (i - 1)};
+    const int fst[2] = {1, nf};
+    cfl = 0.0;
+    for (int d = 0; d < 2; d++) {
+      const int c = cc[d];
+      const int glo = (2 * d) * nc + other[d] - 1, ghi = (2 * d + 1) * nc + other[d] - 1;
+      const bool last = c == nc;
+      double sig_lo, sig_hi = 0.0;
+      const double ex_lo = Ef[face[d]], ex_hi = Ef[face[d] + fst[d]];
+      {
+        // the electrons, as k2_flux
+        const double Lm2 = (c == 1) ? g2[glo] : ne[c0 - 2 * st[d]];
+        const double Lm1 = ne[c0 - st[d]], L0 = ne[c0], Lp1 = ne[c0 + st[d]];
+        const double Lp2 = last ? g2[ghi] : ne[c0 + 2 * st[d]];
+        double vl, dl, mul;
+        face_vd(A, E[c0 - st[d]], E[c0], ex_lo, vl, dl, mul);
+        double u;
+        if (-1 * ex_lo > 0) u = Lm1 + 0.5 * limiter(A.lim, L0 - Lm1, Lm1 - Lm2);
+        else u = L0 - 0.5 * limiter(A.lim, L0 - Lm1, Lp1 - L0);
+        F[face[d]] = vl * u - dl * idx[d] * (L0 - Lm1);
+        sig_lo = mul * u;
+        double vh = 0.0, dh = 0.0, muh = 0.0;
+        face_vd(A, E[c0], E[c0 + st[d]], ex_hi, vh, dh, muh);
+        if (last) {
+          double uh;
+          if (-1 * ex_hi > 0) uh = L0 + 0.5 * limiter(A.lim, Lp1 - L0, L0 - Lm1);
+          else uh = Lp1 - 0.5 * limiter(A.lim, Lp1 - L0, Lp2 - Lp1);
+          F[face[d] + fst[d]] = vh * uh - dh * idx[d] * (Lp1 - L0);
+          sig_hi = muh * uh;
+        }
+        const double mv = fmax(fabs(vh), fabs(vl)), md = fmax(dh, dl);
+        cfl = cfl + (1.0 * mv * idx[d] + 2 * md * (idx[d] * idx[d]));
+      }
+      constexpr int UNR = NI ? NI : 1;
+#pragma unroll UNR
+      for (int n = 0; n < ni; n++) {
+        const double *u_ = I.dens[n] + o;
+        const double *gn = A.gc2 + (size_t)(n + 1) * I.gstride + og;
+        double *Fn = I.F[n] + of;
+        const double q = I.q[n], mu = I.mu[n];
+        const double Lm2 = (c == 1) ? gn[glo] : u_[c0 - 2 * st[d]];
+        const double Lm1 = u_[c0 - st[d]], L0 = u_[c0], Lp1 = u_[c0 + st[d]];
+        double u;
+        if (q * ex_lo > 0) u = Lm1 + 0.5 * limiter(A.lim, L0 - Lm1, Lm1 - Lm2);
+        else u = L0 - 0.5 * limiter(A.lim, L0 - Lm1, Lp1 - L0);
+        Fn[face[d]] = (q * mu * ex_lo) * u;
+        sig_lo = sig_lo + mu * u;
+        if (last) {
+          const double Lp2 = gn[ghi];
+          double uh;
+          if (q * ex_hi > 0) uh = L0 + 0.5 * limiter(A.lim, Lp1 - L0, L0 - Lm1);
+          else uh = Lp1 - 0.5 * limiter(A.lim, Lp1 - L0, Lp2 - Lp1);
+          Fn[face[d] + fst[d]] = (q * mu * ex_hi) * uh;
+          sig_hi = sig_hi + mu * uh;
+        }
+      }
+      smax = fmax(smax, sig_lo);
+      if (last) smax = fmax(smax, sig_hi);
+    }
+  }
+  block_fold<true>(cfl, red);
+  block_fold<true>(smax, red + RED_SHARDS);
+}
+
 // flux_from_children: the face fluxes of a leaf next to refined boxes are
 // the mean of the two fine faces; task = (parent id << 3) | nb
 // CYL (k2_consistent_cyl): on faces normal to z the two fine fluxes are
@@ -1771,12 +1886,23 @@ struct MaskArgs {
   const uint8_t *stat;
 };
 
-template <int NS, bool CYL, bool PHOTO = false, bool MASK = false>
+// IONS (k2_update_ions; a fluid with n_ions > 0): every mobile ion adds the
+// divergence of its own face flux I.F[q] to its species slot I.s[q]
+// (flux_update_densities over all flux variables, m_af_flux_schemes.f90:
+// 386-417), after the electrons and in the same expression; a masked cell
+// gets none of them
+struct IonUpdArgs {
+  int n;
+  int s[AFH_MAX_IONS];
+  const double *F[AFH_MAX_IONS];
+};
+
+template <int NS, bool CYL, bool PHOTO = false, bool MASK = false, bool IONS = false>
 __device__ __forceinline__ void
 update_body(UpdArgs A, const int32_t *__restrict__ ids,
             const afh_box_meta *__restrict__ meta, int nc, int bsz, int fsz,
             unsigned long long *red, PhotoArgs P = PhotoArgs{nullptr, 0},
-            MaskArgs M = MaskArgs{nullptr, nullptr}) {
+            MaskArgs M = MaskArgs{nullptr, nullptr}, IonUpdArgs I = IonUpdArgs{0, {}, {}}) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   double cmin = 1e100;
   const int ns = NS == MAXS ? A.ns : NS;
@@ -1847,10 +1973,33 @@ update_body(UpdArgs A, const int32_t *__restrict__ ids,
     } else {
       y[e] = y[e] + dtx * (F[f0] - F[f0 + 1]) + dty * (F[d2 + f0] - F[d2 + f0 + nf]);
     }
+    if (IONS && !(MASK && !upd)) {
+      double rf1 = 1.0, rf2 = 1.0;
+      if (CYL) cyl_flux_factors(meta[id - 1].r_min[0], meta[id - 1].dr[0], i, rf1, rf2);
+      for (int q = 0; q < I.n; q++) {
+        const double *Fq = I.F[q] + (size_t)(id - 1) * fsz;
+        const int s = I.s[q];
+        if (CYL)
+          y[s] = y[s] + dtx * (rf1 * Fq[f0] - rf2 * Fq[f0 + 1]) +
+                 dty * (Fq[d2 + f0] - Fq[d2 + f0 + nf]);
+        else
+          y[s] = y[s] + dtx * (Fq[f0] - Fq[f0 + 1]) + dty * (Fq[d2 + f0] - Fq[d2 + f0 + nf]);
+      }
+    }
 #pragma unroll
     for (int s = 0; s < ns; s++) A.out[s][x] = y[s];
   }
   if (A.last_step) block_fold<false>(cmin, red);
+}
+
+// the update of a fluid with mobile ions: one entry for the combinations the
+// body serves (Cartesian / cylindrical, photoionization, the update mask)
+template <int NS, bool CYL, bool PHOTO, bool MASK>
+__global__ void __launch_bounds__(NT)
+    k2_update_ions(UpdArgs A, const int32_t *__restrict__ ids,
+                   const afh_box_meta *__restrict__ meta, int nc, int bsz, int fsz,
+                   unsigned long long *red, PhotoArgs P, MaskArgs M, IonUpdArgs I) {
+  update_body<NS, CYL, PHOTO, MASK, true>(A, ids, meta, nc, bsz, fsz, red, P, M, I);
 }
 
 template <int NS>
@@ -2178,6 +2327,12 @@ struct afh_fluid {
   // leaves alone (0: none); per box id whether any cell is updated
   int mask_iv = 0;
   uint8_t *d_mstat = nullptr;
+  // mobile ions (d.n_ions > 0): the second ghost layers of the 1 + n_ions
+  // flux species, [species][box][4][nc] (plane 0 the electrons'), sized for
+  // the tree the fluid is created on -- a regridded tree gets a new fluid --
+  // and each ion's 0-based species slot
+  double *d_gc2 = nullptr;
+  int e_index = -1;
 };
 
 namespace afh2 {
@@ -3473,8 +3628,23 @@ int32_t afh_fluid_create(afh_tree *t, const afh_fluid_desc *d, afh_fluid **out) 
   if (!t || !d || !out) return set_error(AFH_ERR_ARG, "afh_fluid_create: null");
   if (d->n_species < 1 || d->n_species > AFH_MAX_SPECIES)
     return set_error(AFH_ERR_ARG, "afh_fluid_create: n_species");
-  if (d->i_gas_dens || d->n_ions)
-    return set_error(AFH_ERR_UNSUPPORTED, "2-D: variable gas density / mobile ions");
+  if (d->i_gas_dens) return set_error(AFH_ERR_UNSUPPORTED, "2-D: variable gas density");
+  // the ion list, as the 3-D library checks it
+  if (d->n_ions < 0 || d->n_ions > AFH_MAX_IONS)
+    return set_error(AFH_ERR_ARG, "bad mobile ion count");
+  int e_index = -1;
+  for (int s = 0; s < d->n_species; s++)
+    if (d->species_iv[s] == d->i_electron) e_index = s;
+  for (int q = 0; q < d->n_ions; q++) {
+    const int sp = d->ion_species[q];
+    if (sp < 1 || sp > d->n_species || sp - 1 == e_index || d->species_charge[sp - 1] == 0)
+      return set_error(AFH_ERR_ARG, "mobile ion %d: bad species", q + 1);
+    if (d->f_ion_flux[q] < 1 || d->f_ion_flux[q] > t->nvf || d->f_ion_flux[q] == d->f_flux)
+      return set_error(AFH_ERR_ARG, "mobile ion %d: bad flux variable", q + 1);
+    const int iv = d->species_iv[sp - 1];
+    if (iv < 1 || iv > t->nvc || !t->meth[iv].set)
+      return set_error(AFH_ERR_STATE, "set cc methods for mobile ion %d first", q + 1);
+  }
   if (d->i_photo < 0 || d->i_photo > t->nvc ||
       (d->i_photo > 0 && (d->photo_species < 1 || d->photo_species > d->n_species)))
     return set_error(AFH_ERR_ARG, "bad photoionization variable / species");
@@ -3510,6 +3680,9 @@ int32_t afh_fluid_create(afh_tree *t, const afh_fluid_desc *d, afh_fluid **out) 
   }
   H2(hipMalloc(&f->d_reac, sizeof(DevReaction) * R.size()));
   H2(hipMemcpy(f->d_reac, R.data(), sizeof(DevReaction) * R.size(), hipMemcpyHostToDevice));
+  f->e_index = e_index;
+  if (d->n_ions > 0)
+    H2(hipMalloc(&f->d_gc2, sizeof(double) * (size_t)(1 + d->n_ions) * t->nb * 4 * t->nc));
   *out = f;
   return AFH_OK;
 }
@@ -3518,7 +3691,7 @@ int32_t afh_fluid_destroy(afh_fluid *f) {
   if (!f) return AFH_OK;
   hipStreamSynchronize(f->t->stream);
   hipFree(f->d_td), hipFree(f->d_chem), hipFree(f->d_reac);
-  hipFree(f->d_ids), hipFree(f->d_mstat);
+  hipFree(f->d_ids), hipFree(f->d_mstat), hipFree(f->d_gc2);
   delete f;
   return AFH_OK;
 }
@@ -3571,8 +3744,11 @@ static void flux_limits(const double *r, double *dt_lim) {
 
 // fetch = false: the CFL and dielectric maxima stay in slots 0, 1 for
 // afh_fluid_fetch_step
+static int32_t flux_tree_ions(afh_fluid *f, int32_t s_deriv, double *dt_lim, bool fetch);
+
 static int32_t flux_tree(afh_fluid *f, int32_t s_deriv, double *dt_lim, bool fetch = true) {
   afh_tree *t = f->t;
+  if (f->d.n_ions > 0) return flux_tree_ions(f, s_deriv, dt_lim, fetch);
   const int iv = f->d.i_electron + s_deriv;
   if (int32_t e = check_iv(t, iv, "afh_flux_upwind_tree")) return e;
   if (!t->meth[iv].set) return set_error(AFH_ERR_STATE, "flux: no methods for %d", iv);
@@ -3617,6 +3793,94 @@ static int32_t flux_tree(afh_fluid *f, int32_t s_deriv, double *dt_lim, bool fet
   } else if (ntask) {
     hipLaunchKernelGGL(k2_consistent, dim3((ntask * nc + NT - 1) / NT), dim3(NT), 0, t->stream,
                        t->fcv(f->d.f_flux), t->d_boxes, t->cflux.d, ntask, nc, t->fsz);
+    H2_LAUNCH("k2_consistent");
+  }
+  if (!fetch) return AFH_OK;
+  double r[2];
+  if ((e = red_read(t, 0, 2, 3, r))) return e;
+  flux_limits(r, dt_lim);
+  return AFH_OK;
+}
+
+// flux_tree of a fluid with mobile ions: every step over the 1 + n_ions flux
+// species (af_restrict_ref_boundary, af_gc2_box, af_consistent_fluxes), the
+// fluxes of all of them in one launch per level (k2_flux_ions)
+static int32_t flux_tree_ions(afh_fluid *f, int32_t s_deriv, double *dt_lim, bool fetch) {
+  afh_tree *t = f->t;
+  const int nc = t->nc, ni = f->d.n_ions, nsp = 1 + ni;
+  int iv[1 + AFH_MAX_IONS], fv[1 + AFH_MAX_IONS];
+  iv[0] = f->d.i_electron + s_deriv, fv[0] = f->d.f_flux;
+  for (int q = 0; q < ni; q++) {
+    iv[1 + q] = f->d.species_iv[f->d.ion_species[q] - 1] + s_deriv;
+    fv[1 + q] = f->d.f_ion_flux[q];
+  }
+  for (int q = 0; q < nsp; q++) {
+    if (int32_t e = check_iv(t, iv[q], "afh_flux_upwind_tree")) return e;
+    if (!t->meth[iv[q]].set) return set_error(AFH_ERR_STATE, "flux: no methods for %d", iv[q]);
+  }
+  // af_restrict_ref_boundary
+  for (int l = 1; l <= t->nlvl; l++) {
+    const int n = t->refb.n(l);
+    if (!n) continue;
+    for (int q = 0; q < nsp; q++) {
+      restrict_boxes(t, t->ccv(iv[q]), t->refb.at(l), n, true);
+      H2_LAUNCH("k2_restrict");
+    }
+  }
+  int32_t e;
+  if ((e = red_init(t, 0, -HUGE_VAL, 2))) return e;  // CFL and conductivity maxima
+  const size_t gstride = (size_t)t->nb * 4 * nc;
+  FluxArgs A;
+  A.ne = t->ccv(iv[0]), A.E = t->ccv(f->d.i_efld), A.Ef = t->fcv(f->d.f_field);
+  A.F = t->fcv(fv[0]), A.gc2 = f->d_gc2;
+  A.td = dev_lt(f->d.td, f->d_td);
+  A.N_inv = 1 / f->d.gas_number_density;
+  A.lim = f->d.limiter;
+  IonFluxArgs I;
+  I.n = ni, I.gstride = gstride;
+  for (int q = 0; q < AFH_MAX_IONS; q++) {
+    const bool on = q < ni;
+    I.dens[q] = on ? t->ccv(iv[1 + q]) : nullptr;
+    I.F[q] = on ? t->fcv(fv[1 + q]) : nullptr;
+    I.mu[q] = on ? f->d.ion_mobility[q] * A.N_inv : 0.0;
+    const int ch = on ? f->d.species_charge[f->d.ion_species[q] - 1] : 0;
+    I.q[q] = ch > 0 ? 1.0 : ch < 0 ? -1.0 : 0.0;
+  }
+  // level by level, and within a level every gc2 fill before the flux launch
+  // (flux_tree)
+  for (int l = 1; l <= t->nlvl; l++) {
+    const int n = t->leaves.n(l);
+    if (!n) continue;
+    for (int q = 0; q < nsp; q++) {
+      hipLaunchKernelGGL(k2_gc2, grid2(4 * nc, n), blk2(4 * nc), 0, t->stream, t->ccv(iv[q]),
+                         f->d_gc2 + q * gstride, t->d_boxes, t->leaves.at(l), nc, t->bsz,
+                         t->bc4(iv[q]));
+      H2_LAUNCH("k2_gc2");
+    }
+    prof_mark(t, AFH_PROF_FLUX);
+    const dim3 g = grid2(nc * nc, n), bk = blk2(nc * nc);
+    if (ni == 1)
+      hipLaunchKernelGGL(k2_flux_ions<1>, g, bk, 0, t->stream, A, I, t->leaves.at(l), t->d_boxes,
+                         nc, t->bsz, t->fsz, t->red);
+    else if (ni == 6)
+      hipLaunchKernelGGL(k2_flux_ions<6>, g, bk, 0, t->stream, A, I, t->leaves.at(l), t->d_boxes,
+                         nc, t->bsz, t->fsz, t->red);
+    else
+      hipLaunchKernelGGL(k2_flux_ions<0>, g, bk, 0, t->stream, A, I, t->leaves.at(l), t->d_boxes,
+                         nc, t->bsz, t->fsz, t->red);
+    H2_LAUNCH("k2_flux_ions");
+    // k2_flux's 48 B per cell, and per ion one density read and two fluxes written
+    prof_end(t, AFH_PROF_FLUX, (48.0 + 24.0 * ni) * nc * nc * n);
+  }
+  // af_consistent_fluxes of every flux variable
+  const int ntask = t->cflux.off.back();
+  for (int q = 0; q < nsp && ntask; q++) {
+    if (t->cyl())
+      hipLaunchKernelGGL(k2_consistent_cyl, dim3((ntask * nc + NT - 1) / NT), dim3(NT), 0,
+                         t->stream, t->fcv(fv[q]), t->d_boxes, t->cflux.d, ntask, nc, t->fsz);
+    else
+      hipLaunchKernelGGL(k2_consistent, dim3((ntask * nc + NT - 1) / NT), dim3(NT), 0, t->stream,
+                         t->fcv(fv[q]), t->d_boxes, t->cflux.d, ntask, nc, t->fsz);
     H2_LAUNCH("k2_consistent");
   }
   if (!fetch) return AFH_OK;
@@ -3674,7 +3938,36 @@ static int32_t update(afh_fluid *f, double dt, int32_t s_deriv, int32_t n_prev,
     const dim3 bk = blk2(t->nc * t->nc);
     const int32_t *ids = t->leaves.at(l);
     unsigned long long *red = t->red + 2 * RED_SHARDS;
-    if (M.lsf) {
+    if (f->d.n_ions > 0) {
+      // the sibling kernels with the ions' flux divergences
+      const bool photo = f->d.i_photo > 0, cyl = t->cyl(), mask = M.lsf != nullptr;
+      const PhotoArgs P{photo ? t->ccv(f->d.i_photo) : nullptr, f->d.photo_species - 1};
+      IonUpdArgs I;
+      I.n = f->d.n_ions;
+      for (int q = 0; q < AFH_MAX_IONS; q++) {
+        I.s[q] = q < I.n ? f->d.ion_species[q] - 1 : 0;
+        I.F[q] = q < I.n ? t->fcv(f->d.f_ion_flux[q]) : nullptr;
+      }
+      switch (A.ns) {
+#define AFH2_UPDK(N, C, PH, MK)                                                              \
+  hipLaunchKernelGGL((k2_update_ions<N, C, PH, MK>), g, bk, 0, t->stream, A, ids, t->d_boxes, \
+                     t->nc, t->bsz, t->fsz, red, P, M, I)
+#define AFH2_UPD(N)                                    \
+  case N:                                              \
+    if (mask && photo) AFH2_UPDK(N, false, true, true); \
+    else if (mask) AFH2_UPDK(N, false, false, true);    \
+    else if (cyl && photo) AFH2_UPDK(N, true, true, false); \
+    else if (cyl) AFH2_UPDK(N, true, false, false);     \
+    else if (photo) AFH2_UPDK(N, false, true, false);   \
+    else AFH2_UPDK(N, false, false, false);             \
+    break;
+        AFH2_UPD(1) AFH2_UPD(2) AFH2_UPD(3) AFH2_UPD(4) AFH2_UPD(5) AFH2_UPD(6) AFH2_UPD(7)
+        AFH2_UPD(8) AFH2_UPD(9) AFH2_UPD(10) AFH2_UPD(11) AFH2_UPD(12)
+      default: AFH2_UPD(MAXS)
+#undef AFH2_UPD
+#undef AFH2_UPDK
+      }
+    } else if (M.lsf) {
       // the sibling kernels with set_box_mask (and the photoionization term)
       const PhotoArgs P{f->d.i_photo > 0 ? t->ccv(f->d.i_photo) : nullptr,
                         f->d.photo_species - 1};

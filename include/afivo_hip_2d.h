@@ -41,11 +41,14 @@
  * boundaries on the field multigrid: the variable stencils of the boxes the
  * surface crosses in the smoother, residual, FAS restriction and the PFMG
  * level-1 solve, mg_box_lpllsf_gradient, electrode_species_bc, set_box_mask
- * and refine_electrode_dx; below). Not built in 2-D
+ * and refine_electrode_dx; below), and mobile ions (afh_fluid_desc.n_ions,
+ * Cartesian and cylindrical: the fluxes of every flux species with the
+ * per-face conductivity sum, their consistent fluxes and their divergences
+ * in the update). Not built in 2-D
  * (AFH_ERR_UNSUPPORTED or not exported): electrodes in cylindrical
  * coordinates, variable
  * gas density, the temperature rate forms, sharding, ion
- * secondary emission, AFH_COARSE_DIRECT on a cylindrical tree or with a
+ * secondary emission (afh_fluid_set_ion_se_yield, afh_fluid_ion_se_flux), AFH_COARSE_DIRECT on a cylindrical tree or with a
  * level-1 electrode stencil. Built in
  * round 4 for the 2-D time loop (afh.driver over this library,
  * programs/standard_2d/tests/test_2d_rtest.log): the device regrid with the
