@@ -475,7 +475,8 @@ class AfTree:
                "highest_lvl": np.int32(self.highest_lvl),
                "coarse_grid_size": np.array(self.coarse_grid_size, np.int32),
                "r_base": self.r_base.copy(), "dr_base": self.dr_base.copy(),
-               "domain": self.domain.copy()}
+               "domain": self.domain.copy(),
+               "periodic": np.array(self.periodic, np.int32)}
         if nd != 3:
             out["ndim"] = np.int32(nd)
         lvl = np.zeros(nb, np.int32)

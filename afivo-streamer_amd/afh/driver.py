@@ -309,8 +309,19 @@ class Simulation:
         self.log = []
         # mesh: af_init (streamer.f90:151-153)
         nc = c.i("box_size")
+        # periodic (m_streamer.f90:362, af_init's argument in streamer.f90:152):
+        # optional in the case dict, nothing periodic when absent
+        self.periodic = tuple(bool(x) for x in c.d["periodic"]) if "periodic" in c.d \
+            else (False,) * self.ndim
+        if len(self.periodic) != self.ndim:
+            raise ValueError("periodic: %d entries for a %d-D case"
+                             % (len(self.periodic), self.ndim))
+        if any(self.periodic) and self.ndim != 3:
+            raise NotImplementedError("a periodic level-1 solve is built in the 3-D "
+                                      "library only (include/afivo_hip_2d.h)")
         self.af = AfTree(nc, self.origin + self.L, c.ia("coarse_grid_size_value"),
-                         r_min=self.origin, coord=AF_CYL if self.cylindrical else AF_XYZ)
+                         periodic=self.periodic, r_min=self.origin,
+                         coord=AF_CYL if self.cylindrical else AF_XYZ)
         self.tree = self.fluid = self.mg = None
         self.helm = []
         self.shard = None  # shard_over
@@ -471,6 +482,9 @@ class Simulation:
         same state before (e.g. the same deterministic set-up). A refinement
         of the sharded run (adjust_refinement) needs the library's own
         sharding (afh.dist.NativeShard); with the Python Shard it raises."""
+        if any(self.periodic):
+            raise NotImplementedError("a periodic case cannot run sharded: the partition "
+                                      "plans are built from geometry (afh_tree_create_sharded)")
         topo = self.af.topology()
         full = self.tree
         t = self._set_methods(shard.make_tree(self.lib, topo, self.n_var_tree,

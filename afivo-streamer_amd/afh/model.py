@@ -27,8 +27,11 @@ def _lists(topo, kind):
     return _i32(flat), off
 
 
-def tree_desc(topo, n_var_cell, n_var_face, box_capacity=0):
+def tree_desc(topo, n_var_cell, n_var_face, box_capacity=0, periodic=True):
     """afh_tree_desc of a topology dict; returns (desc, arrays it points to).
+    periodic=False clears the topology's periodic flags (its wrapped
+    neighbours stay): the C oracle refuses the flag, and needs it for nothing
+    but the level-1 solve.
     A 2-D topology (topo["ndim"] == 2: ix / r_min / dr of 2, children and
     neighbors of 4, a 3 x 3 neighbor_mat) fills the leading entries of the
     3-D-sized fields (include/afivo_hip_2d.h)."""
@@ -46,7 +49,8 @@ def tree_desc(topo, n_var_cell, n_var_face, box_capacity=0):
     d.n_cell, d.n_boxes, d.highest_lvl = int(topo["nc"]), nb, int(topo["highest_lvl"])
     d.n_var_cell, d.n_var_face = n_var_cell, n_var_face
     d.coarse_grid_size[:] = pad([int(x) for x in topo["coarse_grid_size"]], 1)
-    d.periodic[:] = [0, 0, 0]
+    per = topo.get("periodic", ()) if periodic else ()
+    d.periodic[:] = pad([int(bool(x)) for x in per], 0)
     d.r_base[:] = pad([float(x) for x in topo["r_base"]], 0.0)
     d.dr_base[:] = pad([float(x) for x in topo["dr_base"]], 0.0)
     d.boxes = meta.ctypes.data
@@ -111,14 +115,18 @@ class Tree:
         self.n_var_cell = n_var_cell
         self.n_var_face = n_var_face
         self.box_capacity = int(box_capacity)
-        d, self._keep = tree_desc(topo, n_var_cell, n_var_face, self.box_capacity)
+        # the periodic flags go to the HIP libraries only (the oracle keeps
+        # refusing them, oracle/c/afo.c afo_tree_create)
+        per = lib.prefix != "afo_"
+        d, self._keep = tree_desc(topo, n_var_cell, n_var_face, self.box_capacity, per)
         h = C.c_void_p()
         # sharded: the global id of every stored box, in local-id order (the
         # library stores only the boxes the rank reads, plus one unused id)
         self.global_ids = None
         if shard_of is not None:
             # this rank's boxes of the full tree (afh_tree_create_sharded)
-            full, self._keep_full = tree_desc(shard_of[0], n_var_cell, n_var_face)
+            full, self._keep_full = tree_desc(shard_of[0], n_var_cell, n_var_face,
+                                              periodic=per)
             owner = np.ascontiguousarray(shard_of[1], np.int32)
             pown, rank = owner.ctypes.data_as(capi.P_i32), int(shard_of[2])
             n = C.c_int32()

@@ -326,6 +326,10 @@ int32_t afh_dist_local_ids(const afh_tree_desc *desc, const int32_t *owner, int3
 int32_t afh_tree_create_sharded(const afh_tree_desc *desc, const int32_t *owner, int32_t rank,
                                 int32_t device, afh_tree **out) {
   if (!desc || !owner || !out) return set_error(AFH_ERR_ARG, "afh_tree_create_sharded");
+  // the partition plans are built from geometry (box indices), without wrap
+  if (desc->periodic[0] || desc->periodic[1] || desc->periodic[2])
+    return set_error(AFH_ERR_UNSUPPORTED, "afh_tree_create_sharded: periodic domains are "
+                     "not supported on a sharded tree");
   const Topo t = topo_of(desc);
   Compact c;
   compact(t, desc, std::vector<int32_t>(owner, owner + t.nb), rank, c);

@@ -75,6 +75,9 @@ struct afh_tree {
   int cap = 0;  // boxes the data pools hold (variable stride), >= nb
   size_t bsz = 0, fsz = 0;
   int cgs[3] = {0, 0, 0};
+  // level-1 grid periodic per dimension (afh_tree_desc.periodic): the wrapped
+  // neighbours come with the box records; the level-1 solve wraps by these
+  int periodic[3] = {0, 0, 0};
   double r_base[3], dr_base[3];
   std::vector<afh_box_meta> boxes;  // host copy
   afh_box_meta *d_boxes = nullptr;

@@ -48,6 +48,10 @@ struct CsParams {
   double hc[MAXMG][3];
   double cdiag[MAXMG];
   int bctype[6];
+  // level-1 grid periodic in dimension d: neighbours wrap on every MG level,
+  // the boundary class carries no fold there (cmask drops its two bits)
+  int per[3];
+  int cmask;
   int halo[MAXMG];  // 1: global arrays with a ghost layer, 0: compact (LDS)
   int lg[MAXMG];    // log2(nx) | log2(ny) << 8 when both are powers of 2, else -1
   double *u[MAXMG], *f[MAXMG];
@@ -1970,9 +1974,20 @@ __device__ __forceinline__ size_t gix(const CsParams &P, int m, int i, int j,
 // boundary class of a cell (2 bits per dimension), index into P.dtab
 __device__ __forceinline__ int cs_class(const CsParams &P, int m, int i, int j,
                                         int k) {
-  return (i == 1) | ((i == P.dims[m][0]) << 1) | ((j == 1) << 2) |
-         ((j == P.dims[m][1]) << 3) | ((k == 1) << 4) |
-         ((k == P.dims[m][2]) << 5);
+  return ((i == 1) | ((i == P.dims[m][0]) << 1) | ((j == 1) << 2) |
+          ((j == P.dims[m][1]) << 3) | ((k == 1) << 4) |
+          ((k == P.dims[m][2]) << 5)) &
+         P.cmask;
+}
+
+// neighbour index below / above i on a line of n points: 0 when there is
+// none (a folded physical boundary), the wrapped point when periodic (on a
+// line of 2 points both neighbours are the same point, which enters twice)
+__device__ __forceinline__ int cs_lo(int i, int n, int per) {
+  return i > 1 ? i - 1 : (per ? n : 0);
+}
+__device__ __forceinline__ int cs_hi(int i, int n, int per) {
+  return i < n ? i + 1 : (per ? 1 : 0);
 }
 __device__ __forceinline__ double cs_diag(const CsParams &P, int m, int i,
                                           int j, int k) {
@@ -1989,12 +2004,15 @@ __device__ __forceinline__ void cs_gs_cell(const CsParams &P, int m, int i,
   double *u = P.u[m];
   const double *h = P.hc[m];
   double s = P.f[m][gix(P, m, i, j, k)];
-  if (i > 1) s = s - h[0] * u[gix(P, m, i - 1, j, k)];
-  if (i < nx) s = s - h[0] * u[gix(P, m, i + 1, j, k)];
-  if (j > 1) s = s - h[1] * u[gix(P, m, i, j - 1, k)];
-  if (j < ny) s = s - h[1] * u[gix(P, m, i, j + 1, k)];
-  if (k > 1) s = s - h[2] * u[gix(P, m, i, j, k - 1)];
-  if (k < nz) s = s - h[2] * u[gix(P, m, i, j, k + 1)];
+  const int il = cs_lo(i, nx, P.per[0]), ih = cs_hi(i, nx, P.per[0]);
+  const int jl = cs_lo(j, ny, P.per[1]), jh = cs_hi(j, ny, P.per[1]);
+  const int kl = cs_lo(k, nz, P.per[2]), kh = cs_hi(k, nz, P.per[2]);
+  if (il) s = s - h[0] * u[gix(P, m, il, j, k)];
+  if (ih) s = s - h[0] * u[gix(P, m, ih, j, k)];
+  if (jl) s = s - h[1] * u[gix(P, m, i, jl, k)];
+  if (jh) s = s - h[1] * u[gix(P, m, i, jh, k)];
+  if (kl) s = s - h[2] * u[gix(P, m, i, j, kl)];
+  if (kh) s = s - h[2] * u[gix(P, m, i, j, kh)];
   u[gix(P, m, i, j, k)] = s * cs_inv_diag(P, m, i, j, k);
 }
 
@@ -2006,12 +2024,15 @@ __device__ __forceinline__ double cs_res(const CsParams &P, int m, int i, int j,
   const double *u = P.u[m];
   const double *h = P.hc[m];
   double a = cs_diag(P, m, i, j, k) * u[gix(P, m, i, j, k)];
-  if (i > 1) a = a + h[0] * u[gix(P, m, i - 1, j, k)];
-  if (i < nx) a = a + h[0] * u[gix(P, m, i + 1, j, k)];
-  if (j > 1) a = a + h[1] * u[gix(P, m, i, j - 1, k)];
-  if (j < ny) a = a + h[1] * u[gix(P, m, i, j + 1, k)];
-  if (k > 1) a = a + h[2] * u[gix(P, m, i, j, k - 1)];
-  if (k < nz) a = a + h[2] * u[gix(P, m, i, j, k + 1)];
+  const int il = cs_lo(i, nx, P.per[0]), ih = cs_hi(i, nx, P.per[0]);
+  const int jl = cs_lo(j, ny, P.per[1]), jh = cs_hi(j, ny, P.per[1]);
+  const int kl = cs_lo(k, nz, P.per[2]), kh = cs_hi(k, nz, P.per[2]);
+  if (il) a = a + h[0] * u[gix(P, m, il, j, k)];
+  if (ih) a = a + h[0] * u[gix(P, m, ih, j, k)];
+  if (jl) a = a + h[1] * u[gix(P, m, i, jl, k)];
+  if (jh) a = a + h[1] * u[gix(P, m, i, jh, k)];
+  if (kl) a = a + h[2] * u[gix(P, m, i, j, kl)];
+  if (kh) a = a + h[2] * u[gix(P, m, i, j, kh)];
   return P.f[m][gix(P, m, i, j, k)] - a;
 }
 
@@ -2066,11 +2087,11 @@ __device__ __forceinline__ double cs_refl(const CsParams &P, int c, int i,
   int idx[3] = {i, j, k};
   for (int d = 0; d < 3; d++) {
     if (idx[d] < 1) {
-      idx[d] = 1;
-      if (P.bctype[2 * d] == AFH_BC_DIRICHLET) s = -s;
+      idx[d] = P.per[d] ? P.dims[c][d] : 1;
+      if (!P.per[d] && P.bctype[2 * d] == AFH_BC_DIRICHLET) s = -s;
     } else if (idx[d] > P.dims[c][d]) {
-      idx[d] = P.dims[c][d];
-      if (P.bctype[2 * d + 1] == AFH_BC_DIRICHLET) s = -s;
+      idx[d] = P.per[d] ? 1 : P.dims[c][d];
+      if (!P.per[d] && P.bctype[2 * d + 1] == AFH_BC_DIRICHLET) s = -s;
     }
   }
   return s * P.u[c][gix(P, c, idx[0], idx[1], idx[2])];
@@ -2134,6 +2155,7 @@ constexpr int CS_WAVE_CELLS = 512;
 // generic / flat accesses).
 struct SmLvl {
   int nx, ny, nz, lg;
+  int per, cm;  // periodic dimensions (bit d), CsParams.cmask
   int uo, fo;
   double h0, h1, h2;
 };
@@ -2153,8 +2175,9 @@ struct CsExec {
 };
 
 __device__ __forceinline__ int sm_cls(const SmLvl &L, int i, int j, int k) {
-  return (i == 1) | ((i == L.nx) << 1) | ((j == 1) << 2) | ((j == L.ny) << 3) |
-         ((k == 1) << 4) | ((k == L.nz) << 5);
+  return ((i == 1) | ((i == L.nx) << 1) | ((j == 1) << 2) | ((j == L.ny) << 3) |
+          ((k == 1) << 4) | ((k == L.nz) << 5)) &
+         L.cm;
 }
 
 // cs_gs_cell on a compact LDS level (same operand order)
@@ -2165,11 +2188,17 @@ __device__ __forceinline__ void sm_gs_cell(double *lds, const double *dt,
   const double *u = lds + L.uo;
   double s = lds[L.fo + c];
   if (i > 1) s = s - L.h0 * u[c - 1];
+  else if (L.per & 1) s = s - L.h0 * u[c + (L.nx - 1)];
   if (i < L.nx) s = s - L.h0 * u[c + 1];
+  else if (L.per & 1) s = s - L.h0 * u[c - (L.nx - 1)];
   if (j > 1) s = s - L.h1 * u[c - sy];
+  else if (L.per & 2) s = s - L.h1 * u[c + (L.ny - 1) * sy];
   if (j < L.ny) s = s - L.h1 * u[c + sy];
+  else if (L.per & 2) s = s - L.h1 * u[c - (L.ny - 1) * sy];
   if (k > 1) s = s - L.h2 * u[c - sz];
+  else if (L.per & 4) s = s - L.h2 * u[c + (L.nz - 1) * sz];
   if (k < L.nz) s = s - L.h2 * u[c + sz];
+  else if (L.per & 4) s = s - L.h2 * u[c - (L.nz - 1) * sz];
   lds[L.uo + c] = s * dt[sm_cls(L, i, j, k) * 2 + 1];
 }
 
@@ -2181,11 +2210,17 @@ __device__ __forceinline__ double sm_res(const double *lds, const double *dt,
   const double *u = lds + L.uo;
   double a = dt[sm_cls(L, i, j, k) * 2] * u[c];
   if (i > 1) a = a + L.h0 * u[c - 1];
+  else if (L.per & 1) a = a + L.h0 * u[c + (L.nx - 1)];
   if (i < L.nx) a = a + L.h0 * u[c + 1];
+  else if (L.per & 1) a = a + L.h0 * u[c - (L.nx - 1)];
   if (j > 1) a = a + L.h1 * u[c - sy];
+  else if (L.per & 2) a = a + L.h1 * u[c + (L.ny - 1) * sy];
   if (j < L.ny) a = a + L.h1 * u[c + sy];
+  else if (L.per & 2) a = a + L.h1 * u[c - (L.ny - 1) * sy];
   if (k > 1) a = a + L.h2 * u[c - sz];
+  else if (L.per & 4) a = a + L.h2 * u[c + (L.nz - 1) * sz];
   if (k < L.nz) a = a + L.h2 * u[c + sz];
+  else if (L.per & 4) a = a + L.h2 * u[c - (L.nz - 1) * sz];
   return lds[L.fo + c] - a;
 }
 
@@ -2197,12 +2232,13 @@ __device__ __forceinline__ double sm_refl(const double *lds, const SmLvl &C,
   const int dims[3] = {C.nx, C.ny, C.nz};
 #pragma unroll
   for (int d = 0; d < 3; d++) {
+    const bool per = (C.per >> d) & 1;
     if (idx[d] < 1) {
-      idx[d] = 1;
-      if (bct[2 * d] == AFH_BC_DIRICHLET) s = -s;
+      idx[d] = per ? dims[d] : 1;
+      if (!per && bct[2 * d] == AFH_BC_DIRICHLET) s = -s;
     } else if (idx[d] > dims[d]) {
-      idx[d] = dims[d];
-      if (bct[2 * d + 1] == AFH_BC_DIRICHLET) s = -s;
+      idx[d] = per ? 1 : dims[d];
+      if (!per && bct[2 * d + 1] == AFH_BC_DIRICHLET) s = -s;
     }
   }
   return s * lds[C.uo + ((idx[2] - 1) * C.ny + (idx[1] - 1)) * C.nx + (idx[0] - 1)];
@@ -2355,6 +2391,8 @@ __global__ void __launch_bounds__(1024) k_cs_small(CsParams G, int m0,
       SmLvl &L = s_lv[m];
       L.nx = G.dims[m][0], L.ny = G.dims[m][1], L.nz = G.dims[m][2];
       L.lg = G.lg[m];
+      L.per = (G.per[0] != 0) | ((G.per[1] != 0) << 1) | ((G.per[2] != 0) << 2);
+      L.cm = G.cmask;
       L.h0 = G.hc[m][0], L.h1 = G.hc[m][1], L.h2 = G.hc[m][2];
       const int n = L.nx * L.ny * L.nz;
       L.uo = off;
@@ -2465,7 +2503,7 @@ __global__ void k_cs_gather(CsParams P, const double *__restrict__ phi,
     const int dd = (nb - 1) >> 1;
     const bool low = ((nb - 1) & 1) == 0;
     const bool at = low ? (gi[dd] == 1) : (gi[dd] == P.dims[0][dd]);
-    if (!at) continue;
+    if (!at || P.per[dd]) continue;  // (a periodic face has no boundary value)
     const double cnb = P.hc[0][dd];
     double b2r;
     if (bc[nb - 1].type == AFH_BC_DIRICHLET) b2r = -2 * cnb;
@@ -2558,7 +2596,7 @@ __global__ void __launch_bounds__(1024)
       const int dd = (nb - 1) >> 1;
       const bool low = ((nb - 1) & 1) == 0;
       const bool at = low ? (gi[dd] == 1) : (gi[dd] == P.dims[0][dd]);
-      if (!at) continue;
+      if (!at || P.per[dd]) continue;
       const double cnb = P.hc[0][dd];
       double b2r;
       if (bc[nb - 1].type == AFH_BC_DIRICHLET) b2r = -2 * cnb;
@@ -2757,6 +2795,10 @@ struct afh_mg {
   size_t small_lds = 0;     // LDS bytes of the levels k_cs_small holds
   double *d_dtab = nullptr; // device copy of h_dtab
   std::vector<double> h_dtab;
+  // the bc types the table was built from. The tree's periodic flags need no
+  // place in this key, in q_bc or in the captured V-cycles' keys: a multigrid
+  // stays with its tree, whose flags never change (afh_tree_regrid makes a
+  // new tree with the same flags, and new multigrids with it)
   int tab_bc[6] = {0, 0, 0, 0, 0, 0};
   // fused GSRB pairs (k_gsrb_pair) on levels with at least fused_min boxes
   // (default: enough boxes for one workgroup per CU, 256 tiles)
@@ -2898,7 +2940,7 @@ static int32_t build_table(afh_mg *mg) {
         const int dd = (nb - 1) >> 1;
         const bool low = ((nb - 1) & 1) == 0;
         const int at = low ? (c >> (2 * dd)) & 1 : (c >> (2 * dd + 1)) & 1;
-        if (!at) continue;
+        if (!at || P.per[dd]) continue;  // no fold across a periodic face
         if (bc[nb - 1].type == AFH_BC_DIRICHLET) d = d - P.hc[m][dd];
         else d = d + P.hc[m][dd];
       }
@@ -2917,8 +2959,33 @@ static int32_t build_table(afh_mg *mg) {
 // h tridiag(1, -2, 1) with end diagonals -h (Neumann) / -3h (Dirichlet),
 // diagonalised by a cosine / sine basis; same formula and operation order
 // as oracle/c/afo.c afo_cs_direct_tables.
-static void cs_direct_tables(int n, int bc_lo, int bc_hi, double h, double *q,
-                             double *e) {
+//
+// A periodic dimension's operator is the circulant h tridiag(1, -2, 1) with
+// corners h, diagonalised by the orthonormal real Fourier basis: column 0 the
+// constant, columns 2m-1 / 2m the cos / sin of 2 pi m i / n, the last column
+// the alternating vector when n is even; eigenvalues h (2 cos(2 pi m / n) - 2).
+static void cs_direct_tables(int n, int bc_lo, int bc_hi, int periodic, double h,
+                             double *q, double *e) {
+  if (periodic) {
+    const double pi = 3.14159265358979323846;
+    for (int p = 0; p < n; p++) {
+      const int m = (p + 1) / 2;       // 0, 1, 1, 2, 2, ...
+      const bool is_sin = p > 0 && (p & 1) == 0;
+      const double th = 2 * pi * m / n;
+      double nrm2 = 0.0;
+      for (int i = 0; i < n; i++) {
+        // (2 m = n: cos(pi i) alternates; its sin partner does not exist as
+        // p stops at n - 1)
+        const double v = is_sin ? sin(th * i) : cos(th * i);
+        q[i * n + p] = v;
+        nrm2 = nrm2 + v * v;
+      }
+      const double inv = 1 / sqrt(nrm2);
+      for (int i = 0; i < n; i++) q[i * n + p] = q[i * n + p] * inv;
+      e[p] = h * (2 * cos(th) - 2);
+    }
+    return;
+  }
   const int dlo = bc_lo == AFH_BC_DIRICHLET, dhi = bc_hi == AFH_BC_DIRICHLET;
   const double pi = 3.14159265358979323846;
   for (int p = 0; p < n; p++) {
@@ -2943,7 +3010,7 @@ static int32_t build_direct(afh_mg *mg) {
   for (int d = 0; d < 3; d++) {
     const int n = mg->P.dims[0][d];
     std::vector<double> q((size_t)n * n), qt((size_t)n * n), e(n);
-    cs_direct_tables(n, bc[2 * d].type, bc[2 * d + 1].type, mg->P.hc[0][d],
+    cs_direct_tables(n, bc[2 * d].type, bc[2 * d + 1].type, mg->P.per[d], mg->P.hc[0][d],
                      q.data(), e.data());
     for (int a = 0; a < n; a++)
       for (int b = 0; b < n; b++) qt[(size_t)a * n + b] = q[(size_t)b * n + a];
@@ -2982,6 +3049,17 @@ int32_t afh_mg_create(afh_tree *t, const afh_mg_desc *d, afh_mg **out) {
     return set_error(AFH_ERR_UNSUPPORTED, "coarse solver mode");
   if (!(d->coarse_tol >= 0.0))
     return set_error(AFH_ERR_ARG, "afh_mg_create: coarse_tol %g", d->coarse_tol);
+  const bool any_per = t->periodic[0] || t->periodic[1] || t->periodic[2];
+  if (t->periodic[0] && t->periodic[1] && t->periodic[2] && d->helmholtz_lambda == 0.0)
+    return set_error(AFH_ERR_UNSUPPORTED,
+                     "afh_mg_create: singular operator: a tree periodic in all three "
+                     "dimensions with helmholtz_lambda = 0 (the mean is not subtracted)");
+  if (any_per && d->coarse_mode == AFH_COARSE_PFMG)
+    for (int q = 0; q < 3; q++)
+      if (t->periodic[q] && (t->cgs[q] & (t->cgs[q] - 1)) != 0)
+        return set_error(AFH_ERR_UNSUPPORTED,
+                         "afh_mg_create: AFH_COARSE_PFMG needs a power of two for a periodic "
+                         "level-1 extent, dimension %d has %d cells", q + 1, t->cgs[q]);
   afh_mg *mg = new afh_mg();
   mg->t = t;
   mg->d = *d;
@@ -3016,10 +3094,18 @@ int32_t afh_mg_create(afh_tree *t, const afh_mg_desc *d, afh_mg **out) {
     P.hc[0][q] = mg->lvl_c[0].c[1 + 2 * q];
   }
   P.cdiag[0] = mg->lvl_c[0].c[0];
+  P.cmask = 63;
+  for (int q = 0; q < 3; q++) {
+    P.per[q] = t->periodic[q];
+    if (P.per[q]) P.cmask &= ~(3 << (2 * q));
+  }
   for (;;) {
     int *n = P.dims[m];
     bool ok = (n[0] % 2 == 0) && (n[1] % 2 == 0) && (n[2] % 2 == 0) &&
               n[0] >= 4 && n[1] >= 4 && n[2] >= 4 && m < MAXMG - 1;
+    // red and black stay apart across a seam only on an even count: a
+    // periodic dimension is halved down to 2 points, never to an odd count
+    for (int q = 0; q < 3; q++) ok = ok && !(P.per[q] && (n[q] / 2) % 2 != 0);
     if (!ok) break;
     for (int q = 0; q < 3; q++) {
       P.dims[m + 1][q] = n[q] / 2;
@@ -3944,7 +4030,8 @@ static int32_t pf_prepare(afh_mg *mg) {
             const int dd = (nb - 1) >> 1;
             const bool low = ((nb - 1) & 1) == 0;
             const int dims = t->cgs[dd];
-            if (!(low ? gi[dd] == 1 : gi[dd] == dims)) continue;
+            // (across a periodic face the operator keeps its entry)
+            if (!(low ? gi[dd] == 1 : gi[dd] == dims) || t->periodic[dd]) continue;
             double k2;
             if (bc[nb - 1].type == AFH_BC_DIRICHLET) {
               c[0] = c[0] - c[nb];
@@ -3963,7 +4050,7 @@ static int32_t pf_prepare(afh_mg *mg) {
   AFH_HIP(hipStreamSynchronize(t->stream));
   if (!mg->d_pf_lvl || a7 != mg->pf_a7) {
     afh_pfmg h;
-    if (afh_pfmg_setup(&h, nx, ny, nz, 3, a7.data()))
+    if (afh_pfmg_setup_per(&h, nx, ny, nz, 3, a7.data(), t->periodic))
       return set_error(AFH_ERR_DEVICE, "pfmg: host setup allocation");
     const int np = (int)h.off[h.nl];
     std::vector<PfLvl> lv;

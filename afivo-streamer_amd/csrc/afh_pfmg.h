@@ -43,7 +43,7 @@
  * nx + (i-1); A: 27 coefficients per point, offset (dx, dy, dz) at
  * (dz+1) 9 + (dy+1) 3 + (dx+1) (13 = the centre); P: 2 per point of level l
  * (toward the lower, the upper coarse neighbour along cdir[l]; 0 at even
- * points). C99 and C++.
+ * points). C99 and C++. Periodic directions: afh_pfmg_setup_per, below.
  */
 #ifndef AFH_PFMG_H
 #define AFH_PFMG_H
@@ -68,6 +68,7 @@ typedef struct afh_pfmg {
   double *P;                      /* 2 per point */
   double dxyz[3];                 /* as computed for level 0 */
   int dxyz_flag;
+  int per[3];                     /* direction d periodic (afh_pfmg_setup_per) */
 } afh_pfmg;
 
 static inline int afh_pfmg_s(int dx, int dy, int dz) {
@@ -97,9 +98,28 @@ static inline int afh_pfmg_log2(int n) {
  * the level's point order: centre, -x, +x, -y, +y, -z, +z, the entries
  * toward the outside 0). ndim 2 or 3 (ndim = 2: nz = 1 and no z entries).
  * Returns 0, -1 on allocation failure. */
+static inline int afh_pfmg_setup_per(afh_pfmg *h, int nx, int ny, int nz, int ndim,
+                                     const double *a7, const int *per);
 static inline int afh_pfmg_setup(afh_pfmg *h, int nx, int ny, int nz, int ndim,
                                  const double *a7) {
+  const int none[3] = {0, 0, 0};
+  return afh_pfmg_setup_per(h, nx, ny, nz, ndim, a7, none);
+}
+
+/* The same on a grid periodic in the directions per[d] != 0, whose extents
+ * are powers of two (StructPFMG's own requirement): a7 keeps its entries
+ * across a periodic face, and every index along such a direction wraps --
+ * in the Galerkin product here, in the solve's relaxation, residual,
+ * restriction and interpolation. The even points stay the coarse ones, so
+ * the odd point 1 interpolates from point n (below, by wrap) and point 2.
+ * From 2 points to 1 the odd point's two coarse neighbours are the same
+ * point, and on the 1-point level the offsets -1 and +1 of that direction
+ * fold onto offset 0. With per all zero this is afh_pfmg_setup, operation
+ * for operation. */
+static inline int afh_pfmg_setup_per(afh_pfmg *h, int nx, int ny, int nz, int ndim,
+                                     const double *a7, const int *per) {
   memset(h, 0, sizeof *h);
+  for (int d = 0; d < 3; d++) h->per[d] = per[d] != 0;
   const size_t n0 = (size_t)nx * ny * nz;
   /* PFMGComputeDxyz (SS7 / SS5): the box loop in HYPRE's order, i fastest */
   double cx[3] = {0, 0, 0}, sq[3] = {0, 0, 0};
@@ -254,7 +274,12 @@ static inline int afh_pfmg_setup(afh_pfmg *h, int nx, int ny, int nz, int ndim,
           for (int df = -1; df <= 1; df++) {
             int f[3] = {c[0], c[1], c[2]};
             f[cd] = 2 * c[cd] + df;
-            if (f[cd] < 1 || f[cd] > nf[cd]) continue;
+            /* (fu: the unwrapped index along cd, for the coarse offsets) */
+            const int fu = f[cd];
+            if (f[cd] < 1 || f[cd] > nf[cd]) {
+              if (!h->per[cd]) continue;
+              f[cd] = f[cd] < 1 ? f[cd] + nf[cd] : f[cd] - nf[cd];
+            }
             const size_t fp = afh_pfmg_ix(h, l, f[0], f[1], f[2]);
             const double rw = df == 0 ? 1.0 : (df < 0 ? h->P[2 * fp + 1] : h->P[2 * fp]);
             if (rw == 0.0) continue;
@@ -267,21 +292,29 @@ static inline int afh_pfmg_setup(afh_pfmg *h, int nx, int ny, int nz, int ndim,
               int inside = 1;
               for (int d = 0; d < 3; d++) {
                 g[d] = f[d] + o[d];
-                if (g[d] < 1 || g[d] > nf[d]) inside = 0;
+                if (g[d] < 1 || g[d] > nf[d]) {
+                  if (h->per[d]) g[d] = g[d] < 1 ? g[d] + nf[d] : g[d] - nf[d];
+                  else inside = 0;
+                }
               }
               if (!inside) continue;
               int oc[3] = {o[0], o[1], o[2]};
+              /* the unwrapped index of g along cd: the coarse offsets come
+                 from it (2 c - 2 .. 2 c + 2 gives -1, 0, 1); one coarse
+                 point: every offset along cd is 0 */
+              const int gu = h->per[cd] ? fu + o[cd] : g[cd];
+              const int one = h->per[cd] && nc[cd] == 1;
               if (!(g[cd] & 1)) {
-                oc[cd] = g[cd] / 2 - c[cd];
+                oc[cd] = one ? 0 : gu / 2 - c[cd];
                 Ac[afh_pfmg_s(oc[0], oc[1], oc[2])] += rw * a;
               } else {
                 const size_t gp = afh_pfmg_ix(h, l, g[0], g[1], g[2]);
-                if (g[cd] - 1 >= 2) {
-                  oc[cd] = (g[cd] - 1) / 2 - c[cd];
+                if (g[cd] - 1 >= 2 || h->per[cd]) {
+                  oc[cd] = one ? 0 : (gu - 1) / 2 - c[cd];
                   Ac[afh_pfmg_s(oc[0], oc[1], oc[2])] += rw * a * h->P[2 * gp];
                 }
                 if (g[cd] + 1 <= nf[cd]) {
-                  oc[cd] = (g[cd] + 1) / 2 - c[cd];
+                  oc[cd] = one ? 0 : (gu + 1) / 2 - c[cd];
                   Ac[afh_pfmg_s(oc[0], oc[1], oc[2])] += rw * a * h->P[2 * gp + 1];
                 }
               }

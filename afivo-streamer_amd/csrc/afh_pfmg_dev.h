@@ -38,6 +38,7 @@ struct PfLvl {
   int np;         // points
   uint32_t mask;  // stencil entries nonzero somewhere on the level
   int lgx, lgy;   // log2 n[0], log2 n[1] (-1: not a power of 2)
+  int per;        // bit d: direction d periodic (indices along it wrap)
   double w;       // Jacobi weight
 };
 
@@ -114,8 +115,17 @@ __device__ __forceinline__ double pf_stencil(const PfLvl &L, const double *__res
 #pragma unroll
   for (int s = 0; s < 27; s++) {
     if (!((L.mask >> s) & 1) || (s == 13 && !center)) continue;
-    const int ii = i + s % 3 - 1, jj = j + (s / 3) % 3 - 1, kk = k + s / 9 - 1;
-    if (ii < 1 || ii > L.n[0] || jj < 1 || jj > L.n[1] || kk < 1 || kk > L.n[2]) continue;
+    int ii = i + s % 3 - 1, jj = j + (s / 3) % 3 - 1, kk = k + s / 9 - 1;
+    if (ii < 1 || ii > L.n[0] || jj < 1 || jj > L.n[1] || kk < 1 || kk > L.n[2]) {
+      // outside: no entry, unless the direction is periodic (then the point
+      // across the seam; on 2 points both offsets reach the same point)
+      if (((ii < 1 || ii > L.n[0]) && !(L.per & 1)) || ((jj < 1 || jj > L.n[1]) && !(L.per & 2)) ||
+          ((kk < 1 || kk > L.n[2]) && !(L.per & 4)))
+        continue;
+      ii = ii < 1 ? L.n[0] : ii > L.n[0] ? 1 : ii;
+      jj = jj < 1 ? L.n[1] : jj > L.n[1] ? 1 : jj;
+      kk = kk < 1 ? L.n[2] : kk > L.n[2] ? 1 : kk;
+    }
     const double t = Al[(size_t)s * L.np + p] * x[pf_pt(L, ii, jj, kk)];
     v = SUB ? v - t : v + t;
   }
@@ -184,6 +194,9 @@ __device__ __forceinline__ void pf_restrict(const PfLvl &F, const PfLvl &C,
     if (2 * cc + 1 <= nf) {
       const int q = q0 + st;
       v = v + Pl[q] * src[F.off + q];
+    } else if ((F.per >> cd) & 1) {  // the fine point 1, across the seam
+      const int q = q0 - (nf - 1) * st;
+      v = v + Pl[q] * src[F.off + q];
     }
     b[C.off + p] = v;
   }
@@ -211,6 +224,8 @@ __device__ __forceinline__ void pf_interp(const PfLvl &F, const PfLvl &C,
     } else {
       e = 0.0;
       if (fc >= 3) e = Pl[p] * xc[C.off + pc1 + ((fc - 1) / 2 - 1) * cst];
+      // (point 1 of a periodic direction: the last coarse point, by wrap)
+      else if ((F.per >> cd) & 1) e = Pl[p] * xc[C.off + pc1 + (nf / 2 - 1) * cst];
       if (fc + 1 <= nf) e = e + Pl[(size_t)F.np + p] * xc[C.off + pc1 + ((fc + 1) / 2 - 1) * cst];
     }
     x[F.off + p] = assign ? e : x[F.off + p] + e;
@@ -259,6 +274,7 @@ inline void pf_device_tables(const afh_pfmg &h, std::vector<PfLvl> &lv, std::vec
     L.w = h.w[l];
     L.lgx = lg(L.n[0]);
     L.lgy = lg(L.n[1]);
+    L.per = (h.per[0] != 0) | ((h.per[1] != 0) << 1) | ((h.per[2] != 0) << 2);
     L.mask = 0;
     for (int p = 0; p < L.np; p++)
       for (int s = 0; s < 27; s++) {

@@ -774,8 +774,12 @@ static int32_t tree_create_impl(const afh_tree_desc *d, int32_t device,
     return set_error(AFH_ERR_ARG, "afh_tree_create: bad descriptor");
   if (d->n_cell > 128)
     return set_error(AFH_ERR_UNSUPPORTED, "n_cell > 128 not supported");
-  if (d->periodic[0] || d->periodic[1] || d->periodic[2])
-    return set_error(AFH_ERR_UNSUPPORTED, "periodic domains not supported");
+  for (int q = 0; q < 3; q++)
+    // the level-1 grid wraps in whole boxes of an even cell count
+    if (d->periodic[q] && (d->coarse_grid_size[q] < d->n_cell ||
+                           d->coarse_grid_size[q] % d->n_cell != 0))
+      return set_error(AFH_ERR_ARG, "afh_tree_create: periodic dimension %d of %d cells, "
+                       "boxes of %d", q + 1, d->coarse_grid_size[q], d->n_cell);
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
     return set_error(AFH_ERR_DEVICE, "no HIP device available");
@@ -799,6 +803,7 @@ static int32_t tree_create_impl(const afh_tree_desc *d, int32_t device,
   t->fsz = 3 * (size_t)(t->nc + 1) * (t->nc + 1) * (t->nc + 1);
   for (int q = 0; q < 3; q++) {
     t->cgs[q] = d->coarse_grid_size[q];
+    t->periodic[q] = d->periodic[q] != 0;
     t->r_base[q] = d->r_base[q];
     t->dr_base[q] = d->dr_base[q];
   }
@@ -1493,6 +1498,10 @@ int32_t afh_tree_regrid(afh_tree *o, const afh_tree_desc *d, afh_tree **out) {
   AFH_LIVE(o, "afh_tree_regrid");
   if (d->n_cell != o->nc || d->n_var_cell != o->nvc || d->n_var_face != o->nvf)
     return set_error(AFH_ERR_ARG, "afh_tree_regrid: box size / variables differ");
+  for (int q = 0; q < 3; q++)
+    if ((d->periodic[q] != 0) != (o->periodic[q] != 0))
+      return set_error(AFH_ERR_ARG, "afh_tree_regrid: periodic flags differ from the tree's "
+                       "in dimension %d", q + 1);
   if (o->hook) return set_error(AFH_ERR_UNSUPPORTED, "regrid of a sharded tree");
   afh_tree *t = nullptr;
   int32_t e;

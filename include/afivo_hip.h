@@ -117,6 +117,32 @@ typedef struct afh_tree_desc {
   int32_t n_var_cell;
   int32_t n_var_face;
   int32_t coarse_grid_size[3];
+  /* af_t%periodic (af_init's argument, m_af_core.f90:436-501). The wrapped
+   * neighbours come with the boxes (neighbors / neighbor_mat, as afivo's
+   * create_index_array and set_neighbs store them): the box kernels follow
+   * them and the library never recomputes them. The flag itself makes the
+   * level-1 solve wrap: AFH_COARSE_CYCLES on every level of its hierarchy (a
+   * periodic dimension is halved down to 2 points, never to an odd count;
+   * both neighbours of a point are then the same point, entered twice),
+   * AFH_COARSE_DIRECT with the real Fourier basis of the circulant operator
+   * in that dimension, AFH_COARSE_PFMG with every index along it wrapped in
+   * set-up and solve (csrc/afh_pfmg.h afh_pfmg_setup_per). Rules:
+   *  - a periodic dimension's coarse_grid_size is a multiple of n_cell;
+   *  - afh_tree_regrid with flags that differ from the old tree's:
+   *    AFH_ERR_ARG;
+   *  - afh_tree_create_sharded with any flag set: AFH_ERR_UNSUPPORTED (the
+   *    partition plans are built from geometry);
+   *  - the two afh_bc entries of a periodic dimension (afh_set_cc_methods,
+   *    afh_set_bc) are accepted and never read;
+   *  - afh_mg_create on a tree periodic in all three dimensions with
+   *    helmholtz_lambda == 0: AFH_ERR_UNSUPPORTED (the operator is singular;
+   *    the reference subtracts the mean there, m_af_multigrid.f90:242, which
+   *    is not built). With lambda > 0 it is fine;
+   *  - afh_mg_create with AFH_COARSE_PFMG and a periodic level-1 extent, in
+   *    cells, that is no power of two: AFH_ERR_UNSUPPORTED (StructPFMG's own
+   *    requirement).
+   * The 2-D library records periodic[0] and solves level 1 as if the walls
+   * were physical (include/afivo_hip_2d.h). */
   int32_t periodic[3];
   double r_base[3];
   double dr_base[3];

@@ -49,7 +49,8 @@
  * coordinates, variable
  * gas density, the temperature rate forms, sharding, ion
  * secondary emission (afh_fluid_set_ion_se_yield, afh_fluid_ion_se_flux), AFH_COARSE_DIRECT on a cylindrical tree or with a
- * level-1 electrode stencil. Built in
+ * level-1 electrode stencil, the periodic level-1 solve (afh_tree_desc.periodic
+ * is recorded; level 1 is solved as if the walls were physical). Built in
  * round 4 for the 2-D time loop (afh.driver over this library,
  * programs/standard_2d/tests/test_2d_rtest.log): the device regrid with the
  * prolongation of the automatic variables, default_refinement's flags, the
