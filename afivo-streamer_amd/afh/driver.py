@@ -316,9 +316,8 @@ class Simulation:
         if len(self.periodic) != self.ndim:
             raise ValueError("periodic: %d entries for a %d-D case"
                              % (len(self.periodic), self.ndim))
-        if any(self.periodic) and self.ndim != 3:
-            raise NotImplementedError("a periodic level-1 solve is built in the 3-D "
-                                      "library only (include/afivo_hip_2d.h)")
+        # (the periodic level-1 solve is built in both HIP libraries; the
+        # oracle gets zeros through afh.model.Tree and solves level 1 with walls)
         self.af = AfTree(nc, self.origin + self.L, c.ia("coarse_grid_size_value"),
                          periodic=self.periodic, r_min=self.origin,
                          coord=AF_CYL if self.cylindrical else AF_XYZ)

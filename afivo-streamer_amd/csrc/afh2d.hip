@@ -87,6 +87,7 @@
 #include <vector>
 
 #include "../../include/afivo_hip_2d.h"
+#include "afh_cs_tables.h"
 #include "afh_pfmg_dev.h"
 
 namespace afh2 {
@@ -1257,13 +1258,16 @@ __global__ void __launch_bounds__(NT)
 // 1-D Laplacian with the boundary conditions folded in, as
 // stencil_handle_boundaries does for HYPRE, m_coarse_solver.f90:442-491):
 // gather rhs + boundary terms, Q_x^T, Q_y^T, divide by the eigenvalue sums,
-// Q_y, Q_x, scatter -- in one workgroup, the grid in LDS
+// Q_y, Q_x, scatter -- in one workgroup, the grid in LDS. per: bit d set for a
+// periodic dimension, whose faces carry no boundary term (its table is the
+// real Fourier basis of the circulant, afh_cs_tables.h)
 __global__ void __launch_bounds__(1024)
     k2_cs_direct(double *__restrict__ phi, const double *__restrict__ rhs,
                  const afh_box_meta *__restrict__ meta, const int32_t *__restrict__ ids,
                  int nid, int nc, int bsz, int nx, int ny, double hx, double hy, Bc4 g,
                  const double *__restrict__ qx, const double *__restrict__ qy,
-                 const double *__restrict__ ex, const double *__restrict__ ey, double lam) {
+                 const double *__restrict__ ex, const double *__restrict__ ey, double lam,
+                 int per) {
   __shared__ double A[CS2_CELLS], B[CS2_CELLS];
   const int n2 = nc * nc, ng = nc + 2;
   for (int u = threadIdx.x; u < nid * n2; u += blockDim.x) {
@@ -1278,7 +1282,7 @@ __global__ void __launch_bounds__(1024)
       const int dd = (nb - 1) >> 1;
       const bool low = ((nb - 1) & 1) == 0;
       const bool on = low ? (gi[dd] == 1) : (gi[dd] == dims[dd]);
-      if (!on) continue;
+      if (!on || ((per >> dd) & 1)) continue;
       double b2r;
       if (g.bc[nb - 1].type == AFH_BC_DIRICHLET) b2r = -2 * hc[dd];
       else b2r = -(hc[dd] * m.dr[dd]) * (low ? -1 : 1);
@@ -2225,7 +2229,9 @@ struct afh_tree {
   // once a multigrid or fluid object exists on the tree
   int coord = AFH_COORD_XYZ;
   bool coord_fixed = false;
-  int periodic0 = 0;
+  // level-1 grid periodic per dimension (afh_tree_desc.periodic): the wrapped
+  // neighbours are in the box records, the flags steer the level-1 solve
+  int periodic[2] = {0, 0};
   double r_base0 = 0.0;
   bool cyl() const { return coord == AFH_COORD_CYL; }
   std::vector<afh_box_meta> boxes;
@@ -2280,7 +2286,10 @@ struct afh_mg {
   bool corner_fold = true;
   int nx = 0, ny = 0;
   double *d_q[2] = {nullptr, nullptr}, *d_e[2] = {nullptr, nullptr};
+  // the bc types the tables were built from (a periodic dimension's are
+  // neither read nor compared)
   int q_bc[4] = {0, 0, 0, 0};
+  bool q_built = false;
   // the fused pair (k2_pair_box; AFH_PAIR2D=0: the split half-sweeps) and
   // its spare phi image (config 1: 1.08-1.14 -> 0.85-0.87 ms per step,
   // profiles/r04_push_ab.txt)
@@ -2465,7 +2474,7 @@ int32_t afh_tree_set_coord(afh_tree *t, int32_t coord) {
   if (t->coord_fixed)
     return set_error(AFH_ERR_STATE,
                      "afh_tree_set_coord: after afh_mg_create / afh_fluid_create on the tree");
-  if (coord == AFH_COORD_CYL && t->periodic0)
+  if (coord == AFH_COORD_CYL && t->periodic[0])
     return set_error(AFH_ERR_ARG, "afh_tree_set_coord: cylindrical with a periodic r");
   if (coord == AFH_COORD_CYL && t->r_base0 < 0)
     return set_error(AFH_ERR_ARG, "afh_tree_set_coord: cylindrical with r_base[0] = %g < 0",
@@ -2490,6 +2499,12 @@ int32_t afh_tree_create(const afh_tree_desc *desc, int32_t device, afh_tree **ou
     return set_error(AFH_ERR_ARG, "afh_tree_create: bad sizes");
   // box_capacity (the 3-D in-place regrid) is accepted and not used: a 2-D
   // regrid copies the persisting boxes into the new tree's pools
+  for (int q = 0; q < 2; q++)
+    // the level-1 grid wraps in whole boxes of an even cell count
+    if (desc->periodic[q] && (desc->coarse_grid_size[q] < nc ||
+                              desc->coarse_grid_size[q] % nc != 0))
+      return set_error(AFH_ERR_ARG, "afh_tree_create: periodic dimension %d of %d cells, "
+                       "boxes of %d", q + 1, desc->coarse_grid_size[q], nc);
   if (device >= 0) H2(hipSetDevice(device));
   afh_tree *t = new afh_tree();
   H2(hipGetDevice(&t->device));
@@ -2499,7 +2514,8 @@ int32_t afh_tree_create(const afh_tree_desc *desc, int32_t device, afh_tree **ou
   t->nvc = desc->n_var_cell, t->nvf = desc->n_var_face;
   t->bsz = t->ng * t->ng, t->fsz = 2 * (nc + 1) * (nc + 1);
   t->cgs[0] = desc->coarse_grid_size[0], t->cgs[1] = desc->coarse_grid_size[1];
-  t->periodic0 = desc->periodic[0], t->r_base0 = desc->r_base[0];
+  t->periodic[0] = desc->periodic[0] != 0, t->periodic[1] = desc->periodic[1] != 0;
+  t->r_base0 = desc->r_base[0];
   t->boxes.assign(desc->boxes, desc->boxes + t->nb);
   t->meth.assign(t->nvc + 1, Meth());
   auto lists = [&](const int32_t *a, const int32_t *off) {
@@ -2753,6 +2769,16 @@ int32_t afh_mg_create(afh_tree *t, const afh_mg_desc *d, afh_mg **out) {
                      "diagonalise the operator in r; use AFH_COARSE_PFMG");
   if (d->n_cycle_down < 1 || d->n_cycle_up < 1)
     return set_error(AFH_ERR_ARG, "afh_mg_create: cycles");
+  if (t->periodic[0] && t->periodic[1] && d->helmholtz_lambda == 0.0)
+    return set_error(AFH_ERR_UNSUPPORTED,
+                     "afh_mg_create: singular operator: a tree periodic in both "
+                     "dimensions with helmholtz_lambda = 0 (the mean is not subtracted)");
+  if (d->coarse_mode == AFH_COARSE_PFMG)
+    for (int q = 0; q < 2; q++)
+      if (t->periodic[q] && (t->cgs[q] & (t->cgs[q] - 1)) != 0)
+        return set_error(AFH_ERR_UNSUPPORTED,
+                         "afh_mg_create: AFH_COARSE_PFMG needs a power of two for a periodic "
+                         "level-1 extent, dimension %d has %d cells", q + 1, t->cgs[q]);
   const int nx = t->cgs[0], ny = t->cgs[1];
   if (nx * ny > CS2_CELLS || t->ids.n(1) * t->nc * t->nc != nx * ny)
     return set_error(AFH_ERR_UNSUPPORTED, "2-D: level-1 grid %d x %d", nx, ny);
@@ -2882,28 +2908,6 @@ static const LevelList &cst(const afh_mg *mg, const LevelList &all, const LevelL
   return mg->any_var ? c : all;
 }
 
-// the folded 1-D operator h tridiag(1, -2, 1) with end diagonals -h
-// (Neumann) / -3h (Dirichlet): cosine / sine eigenbasis (same as the 3-D
-// AFH_COARSE_DIRECT tables)
-static void cs_tables(int n, int bc_lo, int bc_hi, double h, double *q, double *e) {
-  const int dlo = bc_lo == AFH_BC_DIRICHLET, dhi = bc_hi == AFH_BC_DIRICHLET;
-  const double pi = 3.14159265358979323846;
-  for (int p = 0; p < n; p++) {
-    double th;
-    if (dlo == dhi) th = pi * (p + dlo) / n;
-    else th = pi * (p + 0.5) / n;
-    double nrm2 = 0.0;
-    for (int i = 0; i < n; i++) {
-      const double v = dlo ? sin(th * (i + 0.5)) : cos(th * (i + 0.5));
-      q[i * n + p] = v;
-      nrm2 = nrm2 + v * v;
-    }
-    const double inv = 1 / sqrt(nrm2);
-    for (int i = 0; i < n; i++) q[i * n + p] = q[i * n + p] * inv;
-    e[p] = h * (2 * cos(th) - 2);
-  }
-}
-
 // AFH_COARSE_PFMG: the folded level-1 operator (stencil_handle_boundaries,
 // the 3-D library's pf_prepare with NDIM = 2), the hierarchy when the
 // boundary types change, then k2_cs_pfmg
@@ -2913,7 +2917,8 @@ static int32_t solve_coarse_pfmg(afh_mg *mg) {
   const int nc = t->nc, nid = t->ids.n(1), nx = mg->nx, ny = mg->ny;
   const size_t n0 = (size_t)nx * ny;
   bool fresh = !mg->d_pf_lvl;
-  for (int q = 0; q < 4; q++) fresh = fresh || mg->pf_bc[q] != M.bc[q].type;
+  for (int q = 0; q < 4; q++)
+    fresh = fresh || (!t->periodic[q >> 1] && mg->pf_bc[q] != M.bc[q].type);
   fresh = fresh || mg->pf_v1_gen != mg->v1_gen;  // a level-1 stencil changed
   if (fresh) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -2947,7 +2952,9 @@ static int32_t solve_coarse_pfmg(afh_mg *mg) {
           for (int nb = 1; nb <= 4; nb++) {
             const int dd = (nb - 1) >> 1;
             const bool low = ((nb - 1) & 1) == 0;
-            if (!(low ? gi[dd] == 1 : gi[dd] == dims[dd])) continue;
+            // (across a periodic face the operator keeps its entry: no fold,
+            // no boundary term; the solve wraps, an electrode box's row too)
+            if (!(low ? gi[dd] == 1 : gi[dd] == dims[dd]) || t->periodic[dd]) continue;
             double k2;
             if (M.bc[nb - 1].type == AFH_BC_DIRICHLET) {
               c[0] = c[0] - c[nb];
@@ -2964,7 +2971,8 @@ static int32_t solve_coarse_pfmg(afh_mg *mg) {
         }
     }
     afh_pfmg h;
-    if (afh_pfmg_setup(&h, nx, ny, 1, 2, a7.data()))
+    const int per[3] = {t->periodic[0], t->periodic[1], 0};
+    if (afh_pfmg_setup_per(&h, nx, ny, 1, 2, a7.data(), per))
       return set_error(AFH_ERR_DEVICE, "pfmg: host setup allocation");
     std::vector<afh_pf::PfLvl> lv;
     std::vector<double> A, P;
@@ -3027,12 +3035,14 @@ static int32_t solve_coarse(afh_mg *mg) {
   afh_tree *t = mg->t;
   const Meth &M = t->meth[mg->d.i_phi];
   for (int q = 0; q < 4; q++) {
+    if (t->periodic[q >> 1]) continue;  // (never read)
     if (M.bc[q].type != AFH_BC_DIRICHLET && M.bc[q].type != AFH_BC_NEUMANN)
       return set_error(AFH_ERR_UNSUPPORTED, "2-D coarse solve: bc type %d", M.bc[q].type);
   }
   if (mg->d.coarse_mode == AFH_COARSE_PFMG) return solve_coarse_pfmg(mg);
-  bool fresh = false;
-  for (int q = 0; q < 4; q++) fresh = fresh || mg->q_bc[q] != M.bc[q].type;
+  bool fresh = !mg->q_built;
+  for (int q = 0; q < 4; q++)
+    fresh = fresh || (!t->periodic[q >> 1] && mg->q_bc[q] != M.bc[q].type);
   const double hx = mg->lvl_c[0].c[1], hy = mg->lvl_c[0].c[3];
   if (fresh) {
     H2(hipStreamSynchronize(t->stream));
@@ -3040,16 +3050,19 @@ static int32_t solve_coarse(afh_mg *mg) {
     const double h[2] = {hx, hy};
     for (int d = 0; d < 2; d++) {
       std::vector<double> q((size_t)n[d] * n[d]), e(n[d]);
-      cs_tables(n[d], M.bc[2 * d].type, M.bc[2 * d + 1].type, h[d], q.data(), e.data());
+      afh2_cs_tables(n[d], M.bc[2 * d].type, M.bc[2 * d + 1].type, t->periodic[d], h[d],
+                     q.data(), e.data());
       H2(hipMemcpy(mg->d_q[d], q.data(), sizeof(double) * q.size(), hipMemcpyHostToDevice));
       H2(hipMemcpy(mg->d_e[d], e.data(), sizeof(double) * e.size(), hipMemcpyHostToDevice));
     }
     for (int q = 0; q < 4; q++) mg->q_bc[q] = M.bc[q].type;
+    mg->q_built = true;
   }
   hipLaunchKernelGGL(k2_cs_direct, dim3(1), dim3(1024), 0, t->stream, t->ccv(mg->d.i_phi),
                      t->ccv(mg->d.i_rhs), t->d_boxes, t->ids.at(1), t->ids.n(1), t->nc, t->bsz,
                      mg->nx, mg->ny, hx, hy, t->bc4(mg->d.i_phi), mg->d_q[0], mg->d_q[1],
-                     mg->d_e[0], mg->d_e[1], mg->d.helmholtz_lambda);
+                     mg->d_e[0], mg->d_e[1], mg->d.helmholtz_lambda,
+                     t->periodic[0] | (t->periodic[1] << 1));
   H2_LAUNCH("k2_cs_direct");
   return gc_lvl(t, 1, mg->d.i_phi, true);
 }
@@ -4551,6 +4564,10 @@ int32_t afh_tree_regrid(afh_tree *o, const afh_tree_desc *d, afh_tree **out) {
   if (!o || !d || !out) return set_error(AFH_ERR_ARG, "afh_tree_regrid: null");
   if (d->n_cell != o->nc || d->n_var_cell != o->nvc || d->n_var_face != o->nvf)
     return set_error(AFH_ERR_ARG, "afh_tree_regrid: box size / variables differ");
+  for (int q = 0; q < 2; q++)
+    if ((d->periodic[q] != 0) != (o->periodic[q] != 0))
+      return set_error(AFH_ERR_ARG, "afh_tree_regrid: periodic flags differ from the tree's "
+                       "in dimension %d", q + 1);
   std::vector<char> in_old(o->nb + 1, 0), keep(d->n_boxes + 1, 0);
   for (const auto &L : o->h_ids)
     for (int32_t id : L) in_old[id] = 1;

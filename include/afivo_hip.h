@@ -141,8 +141,10 @@ typedef struct afh_tree_desc {
    *  - afh_mg_create with AFH_COARSE_PFMG and a periodic level-1 extent, in
    *    cells, that is no power of two: AFH_ERR_UNSUPPORTED (StructPFMG's own
    *    requirement).
-   * The 2-D library records periodic[0] and solves level 1 as if the walls
-   * were physical (include/afivo_hip_2d.h). */
+   * The 2-D library keeps periodic[0..1] under the same rules (both
+   * dimensions periodic with lambda == 0 is its singular case) and wraps in
+   * both of its level-1 solves; AFH_COORD_CYL with a periodic r is refused,
+   * with a periodic z it is allowed (include/afivo_hip_2d.h). */
   int32_t periodic[3];
   double r_base[3];
   double dr_base[3];

@@ -49,8 +49,25 @@
  * coordinates, variable
  * gas density, the temperature rate forms, sharding, ion
  * secondary emission (afh_fluid_set_ion_se_yield, afh_fluid_ion_se_flux), AFH_COARSE_DIRECT on a cylindrical tree or with a
- * level-1 electrode stencil, the periodic level-1 solve (afh_tree_desc.periodic
- * is recorded; level 1 is solved as if the walls were physical). Built in
+ * level-1 electrode stencil, the singular Poisson problem of a tree periodic
+ * in both dimensions (helmholtz_lambda == 0), sharded periodic trees.
+ * Periodic domains (afh_tree_desc.periodic[0..1]; periodic[2] is ignored) are
+ * built under the rules of afivo_hip.h: the box kernels follow the wrapped
+ * neighbours of the box records, and the flags make both level-1 solves wrap
+ * -- AFH_COARSE_DIRECT with the real Fourier tables of the circulant in a
+ * periodic dimension and no boundary term across its faces (the tables stay
+ * per dimension: one may be periodic and the other walled), AFH_COARSE_PFMG
+ * with afh_pfmg_setup_per for ndim = 2, the operator's entries kept across a
+ * periodic face, an electrode box's level-1 row included. afh_tree_create:
+ * AFH_ERR_ARG for a periodic dimension whose coarse_grid_size is no multiple
+ * of n_cell; afh_tree_regrid hands the flags on and returns AFH_ERR_ARG for
+ * other flags; afh_tree_set_coord to AFH_COORD_CYL with a periodic r:
+ * AFH_ERR_ARG (a periodic z is allowed, with AFH_COARSE_PFMG); the two
+ * afh_bc entries of a periodic dimension are accepted and never read;
+ * afh_mg_create: AFH_ERR_UNSUPPORTED for both dimensions periodic with
+ * helmholtz_lambda == 0 ("singular"; lambda > 0 is fine) and for
+ * AFH_COARSE_PFMG with a periodic level-1 extent that is no power of two. A
+ * tree without flags launches what it launched before. Built in
  * round 4 for the 2-D time loop (afh.driver over this library,
  * programs/standard_2d/tests/test_2d_rtest.log): the device regrid with the
  * prolongation of the automatic variables, default_refinement's flags, the
