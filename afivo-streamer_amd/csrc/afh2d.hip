@@ -120,6 +120,7 @@ int32_t check_hip(hipError_t e, const char *what) {
   } while (0)
 
 constexpr int NT = 256;          // threads per workgroup
+constexpr int AFH2_MAX_N_CELL = 1024;  // afh_tree_create (afivo_hip_2d.h)
 constexpr int RED_SHARDS = 256;  // shards of one reduction slot
 constexpr int RED_SLOTS = 4;     // 0 cfl max, 1 sigma max, 2 chem min, 3 |x| max
 constexpr int MAXS = AFH_MAX_SPECIES;
@@ -2494,9 +2495,18 @@ const char *afh_last_error(void) { return afh2::g_err.c_str(); }
 int32_t afh_tree_create(const afh_tree_desc *desc, int32_t device, afh_tree **out) {
   if (!desc || !out || !desc->boxes) return set_error(AFH_ERR_ARG, "afh_tree_create: null");
   const int nc = desc->n_cell;
-  if (nc < 2 || nc % 2 || desc->n_boxes < 1 || desc->highest_lvl < 1 ||
-      desc->n_var_cell < 1 || desc->n_var_face < 0)
+  if (desc->n_boxes < 1 || desc->highest_lvl < 1 || desc->n_var_cell < 1 ||
+      desc->n_var_face < 0)
     return set_error(AFH_ERR_ARG, "afh_tree_create: bad sizes");
+  if (nc < 2 || nc % 2)
+    return set_error(AFH_ERR_ARG, "afh_tree_create: n_cell %d (even, from 2)", nc);
+  // the cylindrical kernels keep a table of 4 nc doubles in dynamic LDS next
+  // to their static arrays, within the 64 KiB a launch gets without asking
+  // for more (nc = 2048 would fill it alone); every other kernel spreads a
+  // box over 256-lane workgroups and has no limit of its own below that
+  if (nc > AFH2_MAX_N_CELL)
+    return set_error(AFH_ERR_UNSUPPORTED, "afh_tree_create: n_cell %d above %d", nc,
+                     AFH2_MAX_N_CELL);
   // box_capacity (the 3-D in-place regrid) is accepted and not used: a 2-D
   // regrid copies the persisting boxes into the new tree's pools
   for (int q = 0; q < 2; q++)

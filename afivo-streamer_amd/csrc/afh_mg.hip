@@ -1857,7 +1857,7 @@ __global__ void k_gradient(const double *__restrict__ phi,
   const int i = t % nc + 1, j = (t / nc) % nc + 1, k = t / (nc * nc) + 1;
   const int ng = nc + 2, nf = nc + 1;
   const double *p = phi + (size_t)(id - 1) * bsz;
-  double *f = fcv + (size_t)(id - 1) * fsz;
+  double *f = fcv ? fcv + (size_t)(id - 1) * fsz : nullptr;
   const size_t c = ix3(ng, i, j, k), sj = ng, sk = (size_t)ng * ng;
   const double ix_ = fac / m.dr[0], iy = fac / m.dr[1], iz = fac / m.dr[2];
   const double fxl = ix_ * (p[c] - p[c - 1]), fxh = ix_ * (p[c + 1] - p[c]);
@@ -1867,12 +1867,14 @@ __global__ void k_gradient(const double *__restrict__ phi,
   auto fx = [&](int d, int a, int b, int cc) {
     return (size_t)d * d3 + ((size_t)(cc - 1) * nf + (b - 1)) * nf + (a - 1);
   };
-  f[fx(0, i, j, k)] = fxl;
-  if (i == nc) f[fx(0, nc + 1, j, k)] = fxh;
-  f[fx(1, i, j, k)] = fyl;
-  if (j == nc) f[fx(1, i, nc + 1, k)] = fyh;
-  f[fx(2, i, j, k)] = fzl;
-  if (k == nc) f[fx(2, i, j, nc + 1)] = fzh;
+  if (fcv) {  // null: the norm only (i_fc = 0)
+    f[fx(0, i, j, k)] = fxl;
+    if (i == nc) f[fx(0, nc + 1, j, k)] = fxh;
+    f[fx(1, i, j, k)] = fyl;
+    if (j == nc) f[fx(1, i, nc + 1, k)] = fyh;
+    f[fx(2, i, j, k)] = fzl;
+    if (k == nc) f[fx(2, i, j, nc + 1)] = fzh;
+  }
   if (nrm) {
     const double a = fxl + fxh, b = fyl + fyh, cc = fzl + fzh;
     nrm[(size_t)(id - 1) * bsz + c] = 0.5 * sqrt(a * a + b * b + cc * cc);
@@ -4627,11 +4629,10 @@ int32_t afh_mg_compute_phi_gradient(afh_mg *mg, int32_t i_fc, double fac,
   case 32: launch_gradient<32>(t, t->ccv(mg->d.i_phi), fcv, nrm, fac, mg->grad_nt); break;
   case 64: launch_gradient<64>(t, t->ccv(mg->d.i_phi), fcv, nrm, fac, mg->grad_nt); break;
   default:
-  if (!fcv) return set_error(AFH_ERR_UNSUPPORTED, "i_fc = 0: box size %d", nc);
-  hipLaunchKernelGGL(k_gradient, dim3((n3 + 255) / 256, ntot), dim3(256), 0,
-                     t->stream, t->ccv(mg->d.i_phi), t->fcv(i_fc),
-                     i_norm > 0 ? t->ccv(i_norm) : nullptr, t->d_boxes,
-                     t->ids.d, nc, t->bsz, t->fsz, fac);
+    // every other box size: one thread per cell, any fcv / nrm combination
+    hipLaunchKernelGGL(k_gradient, dim3((n3 + 255) / 256, ntot), dim3(256), 0,
+                       t->stream, t->ccv(mg->d.i_phi), fcv, nrm, t->d_boxes,
+                       t->ids.d, nc, t->bsz, t->fsz, fac);
   }
   AFH_LAUNCH_CHECK("k_gradient");
   if (!mg->any_lsf) return AFH_OK;

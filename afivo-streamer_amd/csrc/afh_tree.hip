@@ -769,11 +769,12 @@ const char *afh_last_error(void) { return afh::g_err; }
 
 static int32_t tree_create_impl(const afh_tree_desc *d, int32_t device,
                                 afh_tree **out, afh_tree *adopt) {
-  if (!d || !out || d->n_cell < 2 || (d->n_cell & 1) || d->n_boxes < 1 ||
-      d->highest_lvl < 1 || d->n_var_cell < 1)
+  if (!d || !out || d->n_boxes < 1 || d->highest_lvl < 1 || d->n_var_cell < 1)
     return set_error(AFH_ERR_ARG, "afh_tree_create: bad descriptor");
+  if (d->n_cell < 2 || (d->n_cell & 1))
+    return set_error(AFH_ERR_ARG, "afh_tree_create: n_cell %d (even, from 2)", d->n_cell);
   if (d->n_cell > 128)
-    return set_error(AFH_ERR_UNSUPPORTED, "n_cell > 128 not supported");
+    return set_error(AFH_ERR_UNSUPPORTED, "afh_tree_create: n_cell %d above 128", d->n_cell);
   for (int q = 0; q < 3; q++)
     // the level-1 grid wraps in whole boxes of an even cell count
     if (d->periodic[q] && (d->coarse_grid_size[q] < d->n_cell ||

@@ -111,6 +111,17 @@ typedef struct afh_box_meta {
 
 /* The af_t tree (m_af_types.f90:326-393): boxes plus per-level id lists. */
 typedef struct afh_tree_desc {
+  /* Box size: every even n_cell from 2 to 128, as af_init takes them
+   * (m_af_core.f90:160-161 stops on n_cell < 2 or odd). afh_tree_create:
+   * AFH_ERR_ARG for an odd n_cell or one below 2, AFH_ERR_UNSUPPORTED above
+   * 128 (the 2-D library: above 1024, afivo_hip_2d.h); the text names the
+   * size. Every entry point serves every accepted size with the reference's
+   * bits: 4, 8, 16, 32 and 64 have kernels of their own, any other size runs
+   * the general ones (no fused smoother pair, no fused species step: the
+   * switches that ask for them, AFH_GSRB_FUSED_MIN_BOXES and AFH_FE_FUSED,
+   * are then ignored). The one path bound to a size is the 2-D library's
+   * level sets: afh_mg_set_box_lsf with n_cell > 32 is AFH_ERR_UNSUPPORTED
+   * ("box size <n>"). */
   int32_t n_cell;
   int32_t n_boxes; /* highest_id; boxes[0..n_boxes-1] have ids 1..n_boxes */
   int32_t highest_lvl;
@@ -377,8 +388,9 @@ int32_t afh_mg_coarse_iterations(afh_mg *mg, int32_t *n);
  * nothing and returns 0, 0. */
 int32_t afh_mg_graph_stats(afh_mg *mg, int64_t *replays, int64_t *segmented);
 /* mg_compute_phi_gradient (m_af_multigrid.f90:1837-1879) incl. the norm.
- * i_fc = 0 computes the norm i_norm only, on trees without electrode boxes:
- * for a fluid whose flux takes the face field from the potential
+ * i_fc = 0 computes the norm i_norm only, on trees without electrode boxes
+ * (AFH_ERR_ARG with them, or without i_norm) and at every box size: for a
+ * fluid whose flux takes the face field from the potential
  * (afh_fluid_set_field_source), which never reads a stored face field. */
 int32_t afh_mg_compute_phi_gradient(afh_mg *mg, int32_t i_fc, double fac,
                                     int32_t i_norm);

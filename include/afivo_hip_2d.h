@@ -67,7 +67,16 @@
  * afh_mg_create: AFH_ERR_UNSUPPORTED for both dimensions periodic with
  * helmholtz_lambda == 0 ("singular"; lambda > 0 is fine) and for
  * AFH_COARSE_PFMG with a periodic level-1 extent that is no power of two. A
- * tree without flags launches what it launched before. Built in
+ * tree without flags launches what it launched before. Box sizes:
+ * afh_tree_create takes every even n_cell from 2 to 1024 (AFH_ERR_ARG for an
+ * odd one or one below 2; AFH_ERR_UNSUPPORTED above 1024, where the
+ * cylindrical kernels' per-box coefficient table, 32 n_cell bytes, no longer
+ * fits a workgroup's 64 KiB of LDS next to their other arrays; the text
+ * names the size). 4, 8 and 16 have smoother kernels of their own
+ * (AFH_PAIR2D), every other size runs the general ones with the same bits.
+ * Level sets stop at 32: afh_mg_set_box_lsf with n_cell > 32 is
+ * AFH_ERR_UNSUPPORTED ("2-D level sets: box size <n>"; k2_lsf_gradient maps
+ * a box's cells in a 32 x 32 LDS array). Built in
  * round 4 for the 2-D time loop (afh.driver over this library,
  * programs/standard_2d/tests/test_2d_rtest.log): the device regrid with the
  * prolongation of the automatic variables, default_refinement's flags, the

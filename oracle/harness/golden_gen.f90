@@ -32,7 +32,7 @@
 !> are dumped before and after (auto_restrict / auto_prolong / af_gc_box).
 !>
 !> Usage: golden_gen <case> <td_file> <out_dir>
-!>   case = uni4 | amr4 | uni8 | rod8 | regrid8
+!>   case = uni4 | amr4 | uni8 | rod8 | regrid8 | amr2 | amr6 | amr12
 program golden_gen
 #include "cpp_macros.h"
   use m_af_types
@@ -95,6 +95,13 @@ program golden_gen
      nc = 4; grid = [8, 4, 4]; max_lvl = 2; amr_lvl = 4; trace = .false.
   case ("uni8")
      nc = 8; grid = [8, 8, 8]; max_lvl = 2; amr_lvl = 0; trace = .false.
+  case ("amr2")
+     ! the smallest box: a child covers one parent cell
+     nc = 2; grid = [4, 2, 2]; max_lvl = 3; amr_lvl = 5; trace = .false.
+  case ("amr6")
+     nc = 6; grid = [12, 6, 6]; max_lvl = 1; amr_lvl = 2; trace = .false.
+  case ("amr12")
+     nc = 12; grid = [24, 12, 12]; max_lvl = 1; amr_lvl = 2; trace = .false.
   case default
      error stop "unknown case"
   end select

@@ -57,6 +57,12 @@ program golden_gen2d
      nc = 8; grid = [16, 16]; max_lvl = 3; amr_lvl = 0
   case ("amr2d")
      nc = 8; grid = [16, 8]; max_lvl = 2; amr_lvl = 5
+  case ("amr2d2")
+     nc = 2; grid = [4, 2]; max_lvl = 3; amr_lvl = 6
+  case ("amr2d6")
+     nc = 6; grid = [12, 6]; max_lvl = 2; amr_lvl = 5
+  case ("amr2d12")
+     nc = 12; grid = [24, 12]; max_lvl = 2; amr_lvl = 4
   case default
      error stop "unknown case"
   end select

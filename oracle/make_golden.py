@@ -82,7 +82,16 @@ CASES = {
     "amr4": {"chain": CHAIN[:7] + FMG + HELM, "trace": False},
     "rod8": {"chain": ROD, "trace": False, "lsf": True},
     "regrid8": {"chain": REGRID, "trace": False, "regrid": True},
+    # box sizes outside the powers of two 4..64 (the smallest legal one, and
+    # two that no kernel template is instantiated for); amr12 is cut after the
+    # first species update, as amr4 is
+    "amr2": {"chain": CHAIN + FMG + HELM, "trace": False},
+    "amr6": {"chain": CHAIN + FMG + HELM, "trace": False},
+    "amr12": {"chain": CHAIN[:7], "trace": False},
 }
+# no file under tests/golden/ may exceed this; a larger fixture is split over
+# <case>.npz, <case>.p1.npz, ... (tests/golden.py load() merges them)
+PART_LIMIT = 1 << 20
 
 
 def read_topology(path, ndim=3):
@@ -215,7 +224,36 @@ def read_lsf(path, topo):
 CASES_2D = {
     "uni2d": {"chain": CHAIN + FMG + HELM, "trace": False, "ndim": 2},
     "amr2d": {"chain": CHAIN + FMG + HELM, "trace": False, "ndim": 2},
+    "amr2d2": {"chain": CHAIN + FMG + HELM, "trace": False, "ndim": 2},
+    "amr2d6": {"chain": CHAIN + FMG + HELM, "trace": False, "ndim": 2},
+    "amr2d12": {"chain": CHAIN + FMG + HELM, "trace": False, "ndim": 2},
 }
+# the cases from before PART_LIMIT, kept in one file each
+ONE_FILE = ("uni4", "uni8", "amr4", "rod8", "regrid8", "uni2d", "amr2d")
+
+
+def save_parts(case, out):
+    """np.savez_compressed of out, the arrays dealt in order over as many
+    files as PART_LIMIT asks for; returns the paths written."""
+    import glob
+    import zlib
+    base = os.path.join(REPO, "tests", "golden", case)
+    for f in glob.glob(base + ".p[0-9]*.npz"):
+        os.remove(f)
+    parts, used = [{}], 0
+    for k, v in out.items():
+        n = len(zlib.compress(np.ascontiguousarray(v).tobytes(), 6)) + 512
+        if case not in ONE_FILE and parts[-1] and used + n > 0.98 * PART_LIMIT:
+            parts.append({})
+            used = 0
+        parts[-1][k] = v
+        used += n
+    paths = []
+    for i, part in enumerate(parts):
+        paths.append(base + (".p%d.npz" % i if i else ".npz"))
+        np.savez_compressed(paths[-1], **part)
+        assert case in ONE_FILE or os.path.getsize(paths[-1]) <= PART_LIMIT
+    return paths
 
 
 def pack(case, raw_dir):
@@ -274,9 +312,7 @@ def pack(case, raw_dir):
             order.append(name)
             prev = cc
         out["trace_order"] = np.array(order)
-    dst = os.path.join(REPO, "tests", "golden", case + ".npz")
-    np.savez_compressed(dst, **out)
-    return dst
+    return save_parts(case, out)
 
 
 def main():
@@ -291,8 +327,8 @@ def main():
             os.remove(os.path.join(raw, f))
         subprocess.run([gen2d if case in CASES_2D else gen, case, TD_FILE, raw],
                        check=True, stdout=subprocess.DEVNULL)
-        dst = pack(case, raw)
-        print("%-5s -> %s (%.0f kB)" % (case, dst, os.path.getsize(dst) / 1e3))
+        for dst in pack(case, raw):
+            print("%-5s -> %s (%.0f kB)" % (case, dst, os.path.getsize(dst) / 1e3))
 
 
 if __name__ == "__main__":

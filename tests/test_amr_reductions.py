@@ -82,10 +82,14 @@ def sum_ref(topo, v, power):
     return s
 
 
-def random_tree(lib, device, seed=1):
+def random_tree(lib, device, seed=1, nc=8):
     from afh.tree import build_tree
-    topo = build_tree(8, (16, 16, 16), (2e-3,) * 3, 2,
-                      refine=lambda lvl, r0, r1: lvl < 4 and np.all(r0 < 1.1e-3))
+    if nc == 8:
+        topo = build_tree(8, (16, 16, 16), (2e-3,) * 3, 2,
+                          refine=lambda lvl, r0, r1: lvl < 4 and np.all(r0 < 1.1e-3))
+    else:  # 82 boxes on 3 levels
+        from test_hip_parity import size_tree
+        topo = size_tree(nc)
     rng = np.random.default_rng(seed)
     tree = Tree(lib, topo, 2, 0, device=device)
     v = rng.standard_normal(tree.cc_shape) * 1e18
@@ -93,8 +97,8 @@ def random_tree(lib, device, seed=1):
     return topo, tree, v
 
 
-def check_sums_and_locs(lib, device):
-    topo, tree, v = random_tree(lib, device)
+def check_sums_and_locs(lib, device, nc=8):
+    topo, tree, v = random_tree(lib, device, nc=nc)
     for p in (1, 2, 3):
         ref = sum_ref(topo, v, p)
         got = tree.sum_cc(2, p)
@@ -114,7 +118,7 @@ def check_sums_and_locs(lib, device):
                 best = (x, b, q)
         x, b, q = best
         assert val == x and bid == b
-        assert (i - 1) + 8 * (j - 1) + 64 * (k - 1) == q
+        assert (i - 1) + nc * (j - 1) + nc * nc * (k - 1) == q
     return tree
 
 
@@ -125,6 +129,25 @@ def test_sum_and_loc_oracle():
 @pytest.mark.gpu
 def test_sum_and_loc_hip():
     check_sums_and_locs(capi.hip_library(), 0)
+
+
+# box sizes without kernels of their own (cell3's division branch)
+@pytest.mark.parametrize("nc", [6, 12])
+def test_sum_and_loc_oracle_box_size(nc):
+    check_sums_and_locs(capi.oracle_library(), -1, nc)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("nc", [6, 12])
+def test_sum_and_loc_hip_box_size(nc):
+    """The same sums and located extrema, and every one equal to the
+    oracle's to the bit where both reduce in the reference's order (the
+    extrema; the sums to 1e-12 of the numpy restatement, as above)."""
+    th = check_sums_and_locs(capi.hip_library(), 0, nc)
+    to = check_sums_and_locs(capi.oracle_library(), -1, nc)
+    for op in (capi.RED_MAX, capi.RED_MIN, capi.RED_MAXABS):
+        assert th.reduce_loc(2, op) == to.reduce_loc(2, op)
+    assert th.maxabs_cc(2) == to.maxabs_cc(2)
 
 
 def test_retired_tree_after_in_place_regrid():

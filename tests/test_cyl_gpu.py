@@ -197,11 +197,11 @@ def test_residual_bitwise(monkeypatch):
     assert n > 100
 
 
-def _uniform2():
-    """16 x 16 level 1 (2 x 2 boxes) with one uniform refinement."""
+def _uniform2(nc=8):
+    """2 x 2 level-1 boxes of nc^2 with one uniform refinement."""
     c, _, _, _, _ = _state()
     L = c.ra("domain_len")
-    af = AfTree(8, c.ra("domain_origin") + L, [16, 16], r_min=c.ra("domain_origin"))
+    af = AfTree(nc, c.ra("domain_origin") + L, [2 * nc, 2 * nc], r_min=c.ra("domain_origin"))
     af.refine_up_to_lvl(2)
     return af
 
@@ -209,7 +209,7 @@ def _uniform2():
 def _to_global(af, lvl, a, ghosts=False):
     """Level lvl of box array a as one (ny, nx) image (interiors)."""
     nc = af.nc
-    n = 16 * 2 ** (lvl - 1)
+    n = 2 * nc * 2 ** (lvl - 1)
     g = np.zeros((n, n))
     for b in af.lvls[lvl]["ids"]:
         i0, j0 = (af.ix[b][0] - 1) * nc, (af.ix[b][1] - 1) * nc
@@ -233,7 +233,19 @@ def test_down_leg_coarse_rhs(monkeypatch):
     four half sweeps with fills, the residual, its restriction with geometry,
     phi's without, and rhs = L phi + tmp on level 1 -- against numpy on global
     arrays with the boxes' own radii."""
-    af = _uniform2()
+    _down_leg_coarse_rhs(monkeypatch, 8)
+
+
+@pytest.mark.parametrize("nc", [6, 12])
+def test_down_leg_coarse_rhs_box_size(nc, monkeypatch):
+    """The same at box sizes without kernels of their own (k2_gsrb_cyl,
+    k2_residual_cyl, k2_restrict_cyl and k2_parent_rhs_cyl decode by division;
+    the coefficient table of 4 nc doubles)."""
+    _down_leg_coarse_rhs(monkeypatch, nc)
+
+
+def _down_leg_coarse_rhs(monkeypatch, nc):
+    af = _uniform2(nc)
     monkeypatch.setenv("AFH_PAIR2D", "0")
     sim = _sim(True, af=af)
     monkeypatch.delenv("AFH_PAIR2D")
@@ -249,7 +261,6 @@ def test_down_leg_coarse_rhs(monkeypatch):
     got = _to_global(af, 1, sim.tree.get_cc(sim.i_rhs))
     sim.tree.close()
     # numpy
-    nc = af.nc
     c2, c1 = cn.lpl_coef(dr2), cn.lpl_coef(dr1)
     t2 = cn.level_radius_tables(c2, _row_r_mins(af, 2), dr2[0], nc)
     t1 = cn.level_radius_tables(c1, _row_r_mins(af, 1), dr1[0], nc)

@@ -281,7 +281,17 @@ def test_down_leg_bitwise(monkeypatch):
     without the residual pass leaves that rhs on level 1; it holds phi of the
     level-2 boxes after the sweeps through the restricted phi. The level-2
     rhs is the 8 round trips of the whole cycle."""
-    sim = _sim("A", monkeypatch, pair=False)
+    _down_leg(monkeypatch, 8)
+
+
+@pytest.mark.parametrize("nc", [6, 12])
+def test_down_leg_bitwise_box_size(nc, monkeypatch):
+    """The same at box sizes without kernels of their own."""
+    _down_leg(monkeypatch, nc)
+
+
+def _down_leg(monkeypatch, nc):
+    sim = _sim("A", monkeypatch, pair=False, nc=nc)
     af = sim.af
     _start(sim, seed=41)
     phi0, rhs0 = sim.tree.get_cc(sim.i_phi), sim.tree.get_cc(sim.i_rhs)
@@ -294,7 +304,8 @@ def test_down_leg_bitwise(monkeypatch):
     ops = {b: _ops(sim, b) for b in [b1] + l2}
     assert ops[b1] is not None and sum(ops[b] is not None for b in l2) == 2
     sim.tree.close()
-    nc, h = af.nc, af.nc // 2
+    assert nc == af.nc
+    h = nc // 2
     # (put_cc leaves the ghost cells it was given; gc_tree fills the sides)
     P = {b: phi0[b - 1].copy() for b in l2}
     R = {b: rhs0[b - 1].copy() for b in l2}
@@ -344,7 +355,8 @@ def test_vcycles_converge_through_the_electrode(monkeypatch):
     sim.tree.close()
 
 
-@pytest.mark.parametrize("which,nc", [("A", 8), ("B", 8), ("A", 4), ("A", 16)])
+@pytest.mark.parametrize("which,nc", [("A", 8), ("B", 8), ("A", 4), ("A", 16), ("A", 6),
+                                      ("A", 12)])
 def test_fused_variable_pair_equals_split(which, nc, monkeypatch):
     """AFH_PAIR2D=1 (k2_pair_box_v on the levels with variable boxes) against
     AFH_PAIR2D=0 (k2_gsrb + k2_gsrb_v + k2_gc twice), bitwise: after a
@@ -461,7 +473,31 @@ def test_lsf_gradient_bitwise(monkeypatch):
     """Faces and |E| of every box: mg_box_lpl_gradient, on electrode leaves
     then mg_box_lpllsf_gradient in list order and the norm of the corrected
     faces. The rod's lists hold cells with lsf < 0."""
-    sim = _sim("B", monkeypatch)
+    n_corr, n_neg, n_shared = _lsf_gradient(_sim("B", monkeypatch))
+    # (the rod's lists hold no two cells that write one face: that case is
+    # test_lsf_gradient_shared_faces_bitwise)
+    assert n_corr > 20 and n_neg > 0, (n_corr, n_neg, n_shared)
+
+
+@pytest.mark.parametrize("nc", [6, 12, 32])
+def test_lsf_gradient_bitwise_box_size(nc, monkeypatch):
+    """k2_lsf_gradient and k2_gradient on the two-level tree at box sizes
+    without kernels of their own, and at 32, the largest size whose cells the
+    kernel's entry map holds; the electrode's two leaves have corrected
+    faces."""
+    n_corr, _, _ = _lsf_gradient(_sim("A", monkeypatch, nc=nc))
+    assert n_corr > 0
+
+
+def test_lsf_above_32_is_refused(monkeypatch):
+    """afh_mg_set_box_lsf with n_cell > 32: AFH_ERR_UNSUPPORTED, the size in
+    the text (afivo_hip_2d.h); the driver hands its lists over in _bind."""
+    with pytest.raises(capi.AfhError, match="box size 34") as e:
+        _sim("A", monkeypatch, nc=34)
+    assert _code(e) == ERR_UNSUPPORTED
+
+
+def _lsf_gradient(sim):
     af = sim.af
     sim.tree.put_cc(sim.i_phi, _rand(af, 21, abs(sim.voltage)))
     sim.mg.compute_phi_gradient(sim.f_field, -1.0, sim.i_efld)
@@ -490,10 +526,8 @@ def test_lsf_gradient_bitwise(monkeypatch):
         assert np.array_equal(got[0][:nc, :], ref[0][:nc, :]), b
         assert np.array_equal(got[1][:, :nc], ref[1][:, :nc]), b
         assert np.array_equal(nrm[b - 1][1:-1, 1:-1], en.field_norm(ref)), b
-    # (the rod's lists hold no two cells that write one face: that case is
-    # test_lsf_gradient_shared_faces_bitwise)
-    assert n_corr > 20 and n_neg > 0, (n_corr, n_neg, n_shared)
     sim.tree.close()
+    return n_corr, n_neg, n_shared
 
 
 def test_lsf_gradient_shared_faces_bitwise(monkeypatch):

@@ -7,7 +7,7 @@ only (afh_mg_compute_phi_gradient with i_fc = 0) and the flux kernels form
 the same expression from phi and its ghost cells. Both Heun stages must be
 bitwise the stored-field run: |E|, the face fluxes, the densities and the dt
 limits, on uniform trees of every flux kernel's box size (8: k_flux_staged;
-16, 32, 64: k_flux_lds) and on an AMR tree (refinement boundaries, where the
+16, 32, 64: k_flux_lds; 6, 12: no kernel of their own) and on an AMR tree (refinement boundaries, where the
 fine box's face field reads phi's mg_sides_rb ghost cells). The electrode's
 gradient needs the stored face field: i_fc = 0 is refused there. CPU: the C
 oracle; GPU: the HIP library, and HIP == oracle in the new mode."""
@@ -19,6 +19,7 @@ from afh import capi
 from afh.streamer import FV, IV, StreamerCase, tables_from
 from afh.tree import build_tree, uniform_tree
 from test_dist import seed_state
+from test_hip_parity import size_tree
 
 TOPOS = {
     "uni8_l3": lambda: uniform_tree(8, (16, 16, 16), (2e-3, 2e-3, 2e-3), 3),
@@ -30,6 +31,10 @@ TOPOS = {
         16, (32, 32, 32), (2e-3, 2e-3, 2e-3), 2,
         refine=lambda lvl, r0, r1: lvl < 3 and np.all(r0 < 1.2e-3) and np.all(r1 > 0.7e-3)),
     "uni32_l2": lambda: uniform_tree(32, (64, 64, 64), (2e-3, 2e-3, 2e-3), 2),
+    # no template for the size: the general gradient with the norm only,
+    # k_flux_staged without the lane shuffle forming the face field from phi
+    "size6_amr": lambda: size_tree(6),
+    "size12_amr": lambda: size_tree(12),
 }
 # 8 leaf boxes of 64^3 (k_flux_lds<64>): the oracle takes a few seconds
 GPU_TOPOS = dict(TOPOS, uni64_l2=lambda: uniform_tree(64, (128, 128, 128),

@@ -108,6 +108,31 @@ TOPOS = {
 }
 
 
+
+# Box sizes outside the kernels' power-of-two templates 4 .. 64: cell3 /
+# cell3g and the face fills decode by division, every switch (nc) takes its
+# generic kernel, the fused smoother pair is off (AFH_GSRB_FUSED_MIN_BOXES
+# and AFH_FE_FUSED must be ignored, not obeyed), the column kernels run with
+# kc = 2 (nc = 2, 6) and 4 (12, 24) and, where 64 % nc != 0, k_flux_staged
+# without the lane shuffle. nc = 2 is the smallest legal size (a child covers
+# one parent cell, the second ghost layer is cell nc - 1 = 1). 82 boxes on 3
+# levels with coarse-fine faces on levels 2 and 3; uni24_l2: a level without
+# a refinement boundary
+def size_tree(nc):
+    return build_tree(
+        nc, (2 * nc, nc, nc), (2e-3, 1e-3, 1e-3), 2,
+        refine=lambda lvl, r0, r1: lvl < 3 and np.all(r0 < 0.7e-3) and np.all(r1 > 0.3e-3))
+
+
+SIZES = (2, 6, 12, 24)
+SIZE_TOPOS = {"size%d_amr" % nc: (lambda nc=nc: size_tree(nc)) for nc in SIZES}
+SIZE_TOPOS["uni24_l2"] = lambda: uniform_tree(24, (24, 24, 24), (1e-3, 1e-3, 1e-3), 2)
+# 48: the first size outside the templates whose columns run with kc = 8
+SIZE_TOPOS["uni48_l2"] = lambda: uniform_tree(48, (48, 48, 48), (1e-3, 1e-3, 1e-3), 2)
+TOPOS.update(SIZE_TOPOS)
+SIZE_AMR = ["size%d_amr" % nc for nc in SIZES]
+
+
 @pytest.mark.parametrize("coarse", ["mg12", "direct"])
 @pytest.mark.parametrize("name", sorted(TOPOS))
 def test_hip_bitwise_equals_oracle_heun_step(hip, oracle, name, smoother, coarse):
@@ -134,10 +159,12 @@ FE_STEPS = [(0, [0], [1.0], 1), (1, [0, 1], [0.5, 0.5], 0), (1, [0], [1.0], 2),
 
 @pytest.mark.parametrize("fused", ["0", "2"])
 @pytest.mark.parametrize("store", [0, 1])
-@pytest.mark.parametrize("name", ["uni16_l3", "uni32_l2", "uni64_l2", "amr16"])
+@pytest.mark.parametrize("name", ["uni16_l3", "uni32_l2", "uni64_l2", "amr16"]
+                         + sorted(SIZE_TOPOS))
 def test_forward_euler_equals_oracle(hip, oracle, name, store, fused, monkeypatch):
     """afh_fluid_forward_euler (with AFH_FE_FUSED=2: k_fe_lds on trees
-    without coarse-fine flux corrections) gives the bits of the oracle's
+    without coarse-fine flux corrections; at a box size it is not built for
+    the two-call path, silently) gives the bits of the oracle's
     flux_upwind_tree + flux_update_densities: every species state, the dt
     limits, and with store_flux the face fluxes."""
     monkeypatch.setenv("AFH_FE_FUSED", fused)
@@ -204,7 +231,7 @@ def test_multigrids_sharing_a_tree(hip, oracle, name, smoother):
     _assert_same(ca, cb, [IV["phi"], IV["tmp"], IV["rhs"]])
 
 
-@pytest.mark.parametrize("name", ["amr8", "uni16_l3"])
+@pytest.mark.parametrize("name", ["amr8", "uni16_l3"] + SIZE_AMR)
 def test_vcycle_from_stale_ghost_cells(hip, oracle, name, smoother):
     """A V-cycle whose phi has stale ghost cells (as after a regrid: afivo
     fills the ghost cells of the new boxes only, not those of their
@@ -270,7 +297,7 @@ def test_ghost_cells_exact_for_linear_field(hip):
     assert np.max(np.abs(out - phi)) < 1e-13
 
 
-@pytest.mark.parametrize("name", ["amr8", "uni16_l3"])
+@pytest.mark.parametrize("name", ["amr8", "uni16_l3"] + SIZE_AMR)
 def test_fused_maxabs_equals_separate(hip, oracle, name):
     """afh_field_set_rhs_maxabs / afh_mg_fas_vcycle_maxres (the reductions of
     field_compute folded into the rhs and residual passes) give the values of

@@ -68,9 +68,8 @@ def test_hip_refuses_bad_ion_lists():
     bad_ion_fluids(capi.hip_library(), device=0)
 
 
-@pytest.mark.gpu
-def test_hip_mobile_ions_equal_oracle():
-    sim = Simulation(capi.hip_library(), golden.load("case_ions"), device=0)
+def mobile_ions_equal_oracle(case):
+    sim = Simulation(capi.hip_library(), case, device=0)
     sim.start()
     for _ in range(3):
         sim.step()
@@ -92,6 +91,26 @@ def test_hip_mobile_ions_equal_oracle():
     for iv in sim.densities:
         a, b = sim.tree.get_cc(iv), osim.tree.get_cc(iv)
         assert np.max(np.abs(a - b)) <= 1e-12 * np.max(np.abs(b)), sim.cc_names[iv - 1]
+    return sim
+
+
+@pytest.mark.gpu
+def test_hip_mobile_ions_equal_oracle():
+    mobile_ions_equal_oracle(golden.load("case_ions"))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("nc", [6, 12])
+def test_hip_mobile_ions_equal_oracle_box_size(nc):
+    """The same case on boxes of 6^3 and 12^3 (one level-1 box, as the case
+    has): k_flux_ion and k_flux_staged with the division decodes, 6 without
+    the lane shuffle; the driver's start, regrids and three steps at a size
+    no kernel is instantiated for, with the face field taken from phi."""
+    g = dict(golden.load("case_ions"))
+    g["box_size"] = np.array([nc])
+    g["coarse_grid_size_value"] = np.array([nc] * 3)
+    sim = mobile_ions_equal_oracle(g)
+    assert sim.af.nc == nc and sim.faces_from_phi and sim.af.highest_lvl >= 3
 
 
 @pytest.mark.gpu

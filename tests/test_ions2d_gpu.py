@@ -42,23 +42,24 @@ def _refine(af, ix):
     return af.adjust_refinement(fn)
 
 
-def _af(cyl, case=CASE):
+def _af(cyl, case=CASE, nc=8):
     c = Case(golden.load(case))
     L, o = c.ra("domain_len"), c.ra("domain_origin")
-    af = AfTree(8, o + L, [16, 16], r_min=o, coord=AF_CYL if cyl else AF_XYZ)
+    af = AfTree(nc, o + L, [2 * nc, 2 * nc], r_min=o, coord=AF_CYL if cyl else AF_XYZ)
     _refine(af, (1, 1))
     assert af.highest_lvl == 2 and len(af.leaves()) == 7
     return af
 
 
-def _sim(cyl, n_ions, af=None, case=CASE, reactions=True):
+def _sim(cyl, n_ions, af=None, case=CASE, reactions=True, nc=8):
     """A Simulation of `case` bound to the two-level tree (or `af`) with the
     first n_ions of: the case's mobile ions, then every other charged species
     on face variables of its own. Each ion gets a mobility of its own."""
     d = dict(golden.load(case))
-    d["coarse_grid_size_value"] = np.array([16, 16])
+    d["coarse_grid_size_value"] = np.array([2 * nc, 2 * nc])
+    d["box_size"] = np.array([nc])
     sim = Simulation(capi.hip_library_2d(), d, device=0, **PFMG)
-    sim.af = af if af is not None else _af(cyl, case)
+    sim.af = af if af is not None else _af(cyl, case, nc)
     sim.cylindrical = cyl
     plasma_iv = [sim.species_itree[n] for n in sim.plasma]
     ions = list(sim.ions)
@@ -211,7 +212,19 @@ def test_bad_ion_lists_are_refused():
 @pytest.mark.parametrize("n_ions", [1, 6, 7])
 @pytest.mark.parametrize("cyl", [False, True])
 def test_fluxes_and_limits_bitwise(cyl, n_ions):
-    sim = _sim(cyl, n_ions)
+    _fluxes_and_limits(cyl, n_ions, 8)
+
+
+@pytest.mark.parametrize("nc", [6, 12])
+@pytest.mark.parametrize("cyl", [False, True])
+def test_fluxes_and_limits_bitwise_box_size(cyl, nc):
+    """Box sizes without kernels of their own (the t % nc decodes of the flux
+    kernels and of k2_gc2), six ions of both signs."""
+    _fluxes_and_limits(cyl, 6, nc)
+
+
+def _fluxes_and_limits(cyl, n_ions, nc):
+    sim = _sim(cyl, n_ions, nc=nc)
     af = sim.af
     assert len(sim.ions) == n_ions
     if n_ions >= 6:
@@ -231,7 +244,7 @@ def test_fluxes_and_limits_bitwise(cyl, n_ions):
     # the electrons' flux and the CFL limit are those of a fluid without ions
     f_e = sim.tree.get_fc(sim.f_flux)
     sim.tree.close()
-    sim0 = _sim(cyl, 0)
+    sim0 = _sim(cyl, 0, nc=nc)
     assert sim0.ions == []
     for iv, x in before.items():
         sim0.tree.put_cc(iv, x)
@@ -331,7 +344,17 @@ def test_update_densities_bitwise(cyl, n_ions):
     state (1) is zero, so every source vanishes; each flux species ends as the
     previous state (0) plus its own divergence, the others unchanged; ghost
     cells and the refined box of the output state (2) are not written."""
-    sim = _sim(cyl, n_ions)
+    _update_densities(cyl, n_ions, 8)
+
+
+@pytest.mark.parametrize("nc", [6, 12])
+@pytest.mark.parametrize("cyl", [False, True])
+def test_update_densities_bitwise_box_size(cyl, nc):
+    _update_densities(cyl, 6, nc)
+
+
+def _update_densities(cyl, n_ions, nc):
+    sim = _sim(cyl, n_ions, nc=nc)
     af = sim.af
     dt = 2e-12
     _random_state(sim, 7)

@@ -543,7 +543,7 @@ def test_species_step_equals_the_reference():
 
 
 # ----------------------------------------------------------------- smoothers
-@pytest.mark.parametrize("nc", [8, 4, 16])
+@pytest.mark.parametrize("nc", [8, 4, 16, 6, 12])
 def test_down_leg_equals_the_twin(nc, monkeypatch):
     """One V-cycle's down leg on P against the twin, with the fused pair
     (k2_pair_box) and with AFH_PAIR2D=0 (the split half-sweeps). fas_vcycle

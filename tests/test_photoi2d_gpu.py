@@ -83,8 +83,31 @@ def _source_field(af, seed=3):
 # ------------------------------------------------------------------ 1. source
 @pytest.mark.parametrize("cyl", [False, True])
 def test_source_bitwise(cyl):
-    af = _af()
-    sim = _sim(cyl)
+    _source_bitwise(cyl, _af())
+
+
+@pytest.mark.parametrize("nc", [6, 12])
+@pytest.mark.parametrize("cyl", [False, True])
+def test_source_bitwise_box_size(cyl, nc):
+    """Box sizes without kernels of their own: 2 x 2 level-1 boxes of nc^2,
+    one of them refined."""
+    from afh.amr import DO_REF, KEEP_REF
+    from afh.driver import Case
+    c = Case(golden.load(CASE))
+    L, o = c.ra("domain_len"), c.ra("domain_origin")
+    af = AfTree(nc, o + L, [2 * nc, 2 * nc], r_min=o)
+
+    def fn(ids):
+        f = [DO_REF if af.lvl[b] == 1 and tuple(af.ix[b][:2]) == (1, 1) else KEEP_REF
+             for b in ids]
+        return np.array(f), np.zeros(len(ids), np.uint32)
+    af.adjust_refinement(fn)
+    assert af.highest_lvl == 2 and len(af.leaves()) == 7
+    _source_bitwise(cyl, af)
+
+
+def _source_bitwise(cyl, af):
+    sim = _sim(cyl, af)
     rng = np.random.default_rng(17)
     ng = af.nc + 2
     shape = (af.highest_id, ng, ng)
