@@ -20,11 +20,13 @@
 //                 bc_to_gc (173-245), af_gc_interp / af_gc_interp_lim
 //                 (394-451, 503-558), mg_sides_rb (m_af_multigrid.f90:294-417)
 //   k2_corners    af_gc_box_corner + af_corner_gc_extrap (125-170, 860-871)
-//   k2_gsrb       stencil_gsrb_357, 2-D constant branch (m_af_stencil.f90:909-922)
+//   k2_gsrb       stencil_gsrb_357 (m_af_stencil.f90:863-889, 909-922)
+//   k2_pair_box   two half-sweeps and the level fills after each, one launch
 //   k2_residual   residual_box = rhs - stencil_apply_357 (m_af_multigrid.f90:801-810,
-//                 m_af_stencil.f90:421-431), optional leaf max|res|
+//                 m_af_stencil.f90:421-441), optional leaf max|res|
 //   k2_rstr_fas   update_coarse's residual + af_restrict_box of tmp and phi
-//                 (m_af_multigrid.f90:691-727, m_af_restrict.f90:62-103)
+//                 (m_af_multigrid.f90:691-727, m_af_restrict.f90:62-106)
+//   k2_restrict   af_restrict_box (m_af_restrict.f90:62-106)
 //   k2_parent_rhs rhs = L phi + tmp, tmp = phi on the parents (728-737)
 //   k2_corr       correct_children: tmp = phi - tmp, phi += prolong_248
 //                 (624-646, m_af_stencil.f90:716-731, [9, 3, 3, 1] / 16)
@@ -37,41 +39,51 @@
 //   k2_flux       flux_upwind_box (m_af_flux_schemes.f90:715-848) with the
 //                 m_fluid callbacks (src/m_fluid.f90:102-227), Koren
 //   k2_consistent af_consistent_fluxes / flux_from_children (m_af_core.f90:1257-1357)
-//   k2_update     flux_update_densities (m_af_flux_schemes.f90:320-394) +
-//                 add_source_terms / get_rates / get_derivatives (field forms);
-//                 k2_update_photo with the photoionization rate (m_fluid.f90:435-440)
+//   k2_update     flux_update_densities (m_af_flux_schemes.f90:320-417) +
+//                 add_source_terms / get_rates / get_derivatives (field forms)
 //   k2_photoi_src photoionization_rate_from_alpha (src/m_photoi.f90:232-270)
 //   k2_photoi_sum photoi_helmh_compute's clear and per-mode subtraction
 //                 (src/m_photoi_helmh.f90:169, 191-202)
 //
-// Cylindrical coordinates (af_cyl, afh_tree_set_coord): k2_gsrb_cyl,
-// k2_pair_box_cyl, k2_residual_cyl, k2_rstr_fas_cyl, k2_parent_rhs_cyl (the
-// stencil with cylindrical_gradient, m_af_stencil.f90:381-404, 863-889),
-// k2_restrict_cyl (af_restrict_box with af_cyl_child_weights,
-// m_af_restrict.f90:93-106), k2_consistent_cyl (m_af_core.f90:1338-1351),
-// k2_update_cyl (m_af_flux_schemes.f90:395-406), k2_box_sum_cyl (sum_2pr_box,
-// m_af_utils.f90:1008-1024) and the per-cell PFMG level-1 coefficients. They
-// are separate kernels: a Cartesian tree launches exactly what it did before.
+// Each operation is one kernel; what a feature changes in it is a template
+// parameter, so a tree or fluid without the feature runs an instantiation
+// that holds none of its code and carries none of its arguments.
+//
+// The V-cycle's box kernels (k2_gsrb, k2_residual, k2_rstr_fas, k2_restrict,
+// k2_parent_rhs) take the 5-point stencil as a policy: StConst the level's
+// constant stencil, StCyl the same with cylindrical_gradient (m_af_stencil.f90:
+// 381-404, 863-889) from a per-box table in LDS and af_cyl_child_weights in
+// the restriction (m_af_restrict.f90:93-106), StVar the variable stencil of an
+// electrode box with bc_correction (m_af_stencil.f90:433-441). k2_gsrb_v, the
+// variable half-sweep (924-934), is a kernel of its own: every cell's rhs
+// makes the bc_correction round trip, one thread per cell. The fused pair is
+// k2_pair_box<NC, LPB, CYL, VAR>, the species update k2_update<NS, CYL, PHOTO,
+// MASK, IONS>.
+//
+// Cylindrical coordinates (af_cyl, afh_tree_set_coord): StCyl, CYL of the
+// pair and of the update (m_af_flux_schemes.f90:395-406), k2_consistent_cyl
+// (m_af_core.f90:1338-1351), k2_box_sum_cyl (sum_2pr_box, m_af_utils.f90:
+// 1008-1024) and the per-cell PFMG level-1 coefficients.
 //
 // Electrodes (level-set boundaries on a Cartesian tree; afh_mg_set_box_stencil
-// / afh_mg_set_box_lsf): k2_gsrb_v, k2_residual_v, k2_rstr_fas_v,
-// k2_parent_rhs_v (stencil_gsrb_357 / stencil_apply_357, variable branch,
-// m_af_stencil.f90:433-441, 924-934, with bc_correction) on the lists of the
-// boxes that carry a stencil, k2_pair_box_v + k2_rhs_roundtrip (the fused
-// pair on levels with such boxes), the boxes' rows and bc_correction in the
-// PFMG level-1 solve, k2_lsf_gradient (mg_box_lpllsf_gradient,
-// m_af_multigrid.f90:2068-2087, and the norm of the corrected faces),
-// k2_electrode_bc (electrode_species_bc, src/streamer.f90:578-636),
-// k2_update_mask / k2_update_photo_mask + k2_mask_status (set_box_mask,
-// src/m_fluid.f90:469-483) and refine_electrode_dx in k2_refine_flags. Again
-// separate kernels: a tree without electrodes launches what it did before.
+// / afh_mg_set_box_lsf): StVar and k2_gsrb_v on the lists of the boxes that
+// carry a stencil (StConst on the rest of each level), VAR of the pair +
+// k2_rhs_roundtrip on levels with such boxes, the boxes' rows and
+// bc_correction in the PFMG level-1 solve, k2_lsf_gradient
+// (mg_box_lpllsf_gradient, m_af_multigrid.f90:2068-2087, and the norm of the
+// corrected faces), k2_electrode_bc (electrode_species_bc, src/streamer.f90:
+// 578-636), MASK of the update + k2_mask_status (set_box_mask, src/m_fluid.f90:
+// 469-483) and refine_electrode_dx in k2_refine_flags. Not built on a
+// cylindrical tree.
+//
+// Photoionization (afh_fluid_desc.i_photo > 0): k2_photoi_src, k2_photoi_sum
+// and PHOTO of the update (m_fluid.f90:435-440).
 //
 // Mobile ions (afh_fluid_desc.n_ions > 0; src/m_fluid.f90:198-208): k2_gc2 per
 // flux species into the fluid's own second ghost layers, k2_flux_ions (the
 // fluxes of every flux species of a level in one launch, the per-face
 // conductivity sum in registers), k2_consistent[_cyl] per flux variable and
-// k2_update_ions (update_body with the ions' divergences). A fluid without
-// ions launches what it did before.
+// IONS of the update (the ions' divergences).
 #include <hip/hip_runtime.h>
 #include <float.h>
 #include <math.h>
@@ -84,6 +96,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/afivo_hip_2d.h"
@@ -332,9 +345,7 @@ struct Coef2 {
   double inv_c1;
 };
 
-// ---- cylindrical coordinates (af_cyl: first index r, second z). The
-// Cartesian kernels keep their code and arguments; a cylindrical tree
-// launches the *_cyl kernels below instead.
+// ---- cylindrical coordinates (af_cyl: first index r, second z)
 //
 // The Laplacian stays the constant stencil with cylindrical_gradient set
 // (m_af_multigrid.f90:1227-1243): per first index i the entries are
@@ -378,56 +389,6 @@ __device__ __forceinline__ void cyl_table(double *T, const Coef2 &cf, const afh_
   for (int i = threadIdx.x; i < nc; i += blockDim.x)
     cyl_coef(cf, m.r_min[0], m.dr[0], i + 1, T + 4 * i);
   __syncthreads();
-}
-
-// stencil_apply_357's cylindrical branch: q the table entry of the cell's i
-__device__ __forceinline__ double apply5_cyl(const double *p, int x, int ng, const double *q,
-                                             const Coef2 &cf) {
-  return q[0] * p[x] + q[1] * p[x - 1] + q[2] * p[x + 1] + cf.c[3] * p[x - ng] +
-         cf.c[4] * p[x + ng];
-}
-
-// stencil_gsrb_357, cylindrical_gradient (m_af_stencil.f90:863-889); 4 nc
-// doubles of dynamic LDS
-__global__ void __launch_bounds__(NT)
-    k2_gsrb_cyl(double *__restrict__ phi, const double *__restrict__ rhs,
-                const afh_box_meta *__restrict__ meta, const int32_t *__restrict__ ids, int nc,
-                int bsz, Coef2 cf, int redblack) {
-  extern __shared__ double cyl_T[];
-  const int id = ids[blockIdx.y];
-  cyl_table(cyl_T, cf, meta[id - 1], nc);
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  const int half = nc >> 1;
-  if (t >= nc * half) return;
-  const int j = t / half + 1, q = t % half;
-  const int i0 = 2 - ((redblack ^ j) & 1);
-  const int i = i0 + 2 * q;
-  const int ng = nc + 2;
-  const size_t o = (size_t)(id - 1) * bsz;
-  double *p = phi + o;
-  const int x = ix2(ng, i, j);
-  const double *c = cyl_T + 4 * (i - 1);
-  p[x] = (rhs[o + x] - c[1] * p[x - 1] - c[2] * p[x + 1] - cf.c[3] * p[x - ng] -
-          cf.c[4] * p[x + ng]) *
-         c[3];
-}
-
-__global__ void __launch_bounds__(NT)
-    k2_gsrb(double *__restrict__ phi, const double *__restrict__ rhs,
-            const int32_t *__restrict__ ids, int nc, int bsz, Coef2 cf, int redblack) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  const int half = nc >> 1;
-  if (t >= nc * half) return;
-  const int j = t / half + 1, q = t % half;
-  const int i0 = 2 - ((redblack ^ j) & 1);  // i0 = 2 - iand(ieor(redblack, j), 1)
-  const int i = i0 + 2 * q;
-  const int ng = nc + 2;
-  const size_t o = (size_t)(ids[blockIdx.y] - 1) * bsz;
-  double *p = phi + o;
-  const int x = ix2(ng, i, j);
-  p[x] = (rhs[o + x] - cf.c[1] * p[x - 1] - cf.c[2] * p[x + 1] - cf.c[3] * p[x - ng] -
-          cf.c[4] * p[x + ng]) *
-         cf.inv_c1;
 }
 
 // A face ghost of box m the level fill would write (k2_gc's physical and
@@ -488,115 +449,40 @@ __device__ __forceinline__ double gc2_face(const double *__restrict__ coarse,
 // LPB lanes per box, 64 / LPB boxes per one-wave workgroup (8^2 boxes: 32
 // lanes, one per cell of a half-sweep, two boxes per wave; the lanes of a
 // missing last box load a copy of box n and store nothing)
-template <int NC, int LPB = 64>
-__global__ void __launch_bounds__(64)
-    k2_pair_box(const double *__restrict__ src, double *__restrict__ dst,
-                const double *__restrict__ rhs, const double *__restrict__ coarse,
-                const afh_box_meta *__restrict__ meta, const int32_t *__restrict__ ids,
-                int n, int bsz, Coef2 cf, Bc4 g) {
-  constexpr int NG = NC + 2, NB = NG * NG, NT = LPB, H = NC / 2, PW = 64 / LPB;
-  __shared__ double P_[PW][NB];
-  const int sub = threadIdx.x / LPB, tid = threadIdx.x % LPB;
-  const int bidx = blockIdx.x * PW + sub;
-  const bool valid = bidx < n;
-  double *P = P_[sub];
-  const int id = ids[valid ? bidx : n - 1];
-  const afh_box_meta &m = meta[id - 1];
-  const double *x = src + (size_t)(id - 1) * bsz, *r = rhs + (size_t)(id - 1) * bsz;
-  double *y = dst + (size_t)(id - 1) * bsz;
-  for (int e = tid; e < NB; e += NT) P[e] = x[e];
-  // B inputs: the odd ghost u < 2 NC (face u / H + 1, its odd positions) of
-  // a same-level neighbour -- the neighbour's boundary cell, its four
-  // neighbours and rhs, loaded before A
-  constexpr int NGH = 2 * NC, GPT = (NGH + NT - 1) / NT;
-  double bl[GPT][5];
-  for (int q = 0; q < GPT; q++) {
-    const int u = tid + NT * q;
-    for (int k = 0; k < 5; k++) bl[q][k] = 0.0;
-    if (u >= NGH) continue;
-    const int nb = u / H + 1, d = (nb - 1) >> 1;
-    const bool low = ((nb - 1) & 1) == 0;
-    const int gi = low ? 0 : NC + 1;
-    const int a = 2 * (u % H) + 1 + ((gi & 1) ? 1 : 0);  // gi + a odd
-    const int nid = m.neighbors[nb - 1];
-    if (nid > 0) {
-      auto at = [&](int n, int tg) { return d == 0 ? ix2(NG, n, tg) : ix2(NG, tg, n); };
-      const double *xs = src + (size_t)(nid - 1) * bsz;
-      const int c = at(low ? NC : 1, a);
-      bl[q][0] = xs[c - 1];
-      bl[q][1] = xs[c + 1];
-      bl[q][2] = xs[c - NG];
-      bl[q][3] = xs[c + NG];
-      bl[q][4] = rhs[(size_t)(nid - 1) * bsz + c];
-    }
-  }
-  __syncthreads();
-  // A: odd cells (k2_gsrb with an odd red-black counter)
-  for (int q = tid; q < NC * H; q += NT) {
-    const int j = q / H + 1, i = 2 - ((1 ^ j) & 1) + 2 * (q % H);
-    const int c = ix2(NG, i, j);
-    P[c] = (r[c] - cf.c[1] * P[c - 1] - cf.c[2] * P[c + 1] - cf.c[3] * P[c - NG] -
-            cf.c[4] * P[c + NG]) *
-           cf.inv_c1;
-  }
-  __syncthreads();
-  // B: odd face ghosts
-  for (int q = 0; q < GPT; q++) {
-    const int u = tid + NT * q;
-    if (u >= NGH) continue;
-    const int nb = u / H + 1, d = (nb - 1) >> 1;
-    const bool low = ((nb - 1) & 1) == 0;
-    const int gi = low ? 0 : NC + 1, i1 = low ? 1 : NC, i2 = low ? 2 : NC - 1;
-    const int a = 2 * (u % H) + 1 + ((gi & 1) ? 1 : 0);
-    auto at = [&](int n, int tg) { return d == 0 ? ix2(NG, n, tg) : ix2(NG, tg, n); };
-    const int nid = m.neighbors[nb - 1];
-    double v;
-    if (nid > 0)
-      v = (bl[q][4] - cf.c[1] * bl[q][0] - cf.c[2] * bl[q][1] - cf.c[3] * bl[q][2] -
-           cf.c[4] * bl[q][3]) *
-          cf.inv_c1;
-    else
-      v = gc2_face(coarse, meta, m, nb, nid, a, P[at(i1, a)], P[at(i2, a)], NC, bsz, g);
-    P[at(gi, a)] = v;
-  }
-  __syncthreads();
-  // C: even cells
-  for (int q = tid; q < NC * H; q += NT) {
-    const int j = q / H + 1, i = 2 - ((0 ^ j) & 1) + 2 * (q % H);
-    const int c = ix2(NG, i, j);
-    P[c] = (r[c] - cf.c[1] * P[c - 1] - cf.c[2] * P[c + 1] - cf.c[3] * P[c - NG] -
-            cf.c[4] * P[c + NG]) *
-           cf.inv_c1;
-  }
-  __syncthreads();
-  // store: interior and corners; the four faces' ghosts pushed
-  for (int e = tid; e < NB; e += NT) {
-    const int i = e % NG, j = e / NG;
-    const int nout = (i == 0 || i == NG - 1) + (j == 0 || j == NG - 1);
-    if (valid && nout != 1) y[e] = P[e];
-  }
-  for (int u = valid ? tid : 4 * NC; u < 4 * NC; u += NT) {
-    const int nb = u / NC + 1, a = u % NC + 1, d = (nb - 1) >> 1;
-    const bool low = ((nb - 1) & 1) == 0;
-    const int gi = low ? 0 : NC + 1, i1 = low ? 1 : NC, i2 = low ? 2 : NC - 1;
-    auto at = [&](int n, int tg) { return d == 0 ? ix2(NG, n, tg) : ix2(NG, tg, n); };
-    const int nid = m.neighbors[nb - 1];
-    if (nid > 0)
-      dst[(size_t)(nid - 1) * bsz + at(low ? NC + 1 : 0, a)] = P[at(i1, a)];
-    else
-      y[at(gi, a)] = gc2_face(coarse, meta, m, nb, nid, a, P[at(i1, a)], P[at(i2, a)], NC,
-                              bsz, g);
-  }
-}
-
-// The pair once more for a cylindrical tree (k2_pair_box_cyl; CYL = true is
-// the only instantiation -- the Cartesian kernel above keeps its own text, so
-// that its code is what it was). Its table T holds the
+//
+// CYL (a cylindrical tree): the table T holds the
 // box's own entries 0 .. NC-1 and, for phase B across an r-face, the
 // same-level neighbour's boundary cell built from the neighbour's own r_min
 // and index (entry NC: the low neighbour's cell NC, NC+1: the high
 // neighbour's cell 1; this box's r_min -+ NC dr can differ in the last bit).
 // A z-neighbour of the same level has this box's radii.
+//
+// VAR (a level with electrode boxes; PairVarArgs, beside the Bc4 in gv): vp /
+// bp: per box id the
+// variable stencil v(5, nc, nc) and bc_correction(nc, nc), or null. A box's
+// own cells take its stencil when it has one (k2_gsrb_v: divided by v(1)),
+// the recomputed boundary cell of a same-level neighbour takes the
+// neighbour's, every other cell cf (k2_gsrb: times inv_c1). The split
+// half-sweeps leave rhs = (rhs + b) - b after each one; here rhs is read
+// only, so half-sweep s of the leg forms the value the s - 1 earlier round
+// trips would have left (pend = those before phase A) and adds b;
+// k2_rhs_roundtrip stores the leg's round trips afterwards. Bitwise k2_gsrb +
+// k2_gsrb_v + k2_gc twice.
+
+// the argument block of a compile-time feature of a kernel: T where the
+// feature is on, empty where it is off. The blocks are bases of one argument
+// struct (an empty base takes no room in it; K tells the empty ones of a
+// struct apart), so a kernel carries the blocks of its own features only.
+template <int K> struct NoArgs {};
+template <bool ON, class T, int K = 0> using ArgsIf = std::conditional_t<ON, T, NoArgs<K>>;
+template <int V> using Int = std::integral_constant<int, V>;  // a compile-time case
+
+struct PairVarArgs {
+  const double *const *vp, *const *bp;
+  int pend;
+};
+template <bool VAR> struct PairBc : Bc4, ArgsIf<VAR, PairVarArgs> {};
+
 // rhs + bc_correction as half-sweep number np + 1 of a leg reads it (VAR)
 __device__ __forceinline__ double pair_rhs_in(double rv, const double *b, int cv, int np) {
   if (!b) return rv;
@@ -605,14 +491,17 @@ __device__ __forceinline__ double pair_rhs_in(double rv, const double *b, int cv
   return rv + bv;
 }
 
-template <int NC, int LPB, bool CYL, bool VAR = false>
-__device__ __forceinline__ void
-pair_box_body(const double *__restrict__ src, double *__restrict__ dst,
-              const double *__restrict__ rhs, const double *__restrict__ coarse,
-              const afh_box_meta *__restrict__ meta, const int32_t *__restrict__ ids, int n,
-              int bsz, Coef2 cf, Bc4 g, const double *const *__restrict__ vp = nullptr,
-              const double *const *__restrict__ bp = nullptr, int pend = 0) {
+template <int NC, int LPB, bool CYL, bool VAR>
+__global__ void __launch_bounds__(64)
+    k2_pair_box(const double *__restrict__ src, double *__restrict__ dst,
+                const double *__restrict__ rhs, const double *__restrict__ coarse,
+                const afh_box_meta *__restrict__ meta, const int32_t *__restrict__ ids, int n,
+                int bsz, Coef2 cf, PairBc<VAR> gv) {
   static_assert(!(CYL && VAR), "electrode stencils on a cylindrical tree are not built");
+  const Bc4 &g = gv;
+  const double *const *vp = nullptr, *const *bp = nullptr;
+  int pend = 0;
+  if constexpr (VAR) vp = gv.vp, bp = gv.bp, pend = gv.pend;
   constexpr int NG = NC + 2, NB = NG * NG, NT = LPB, H = NC / 2, PW = 64 / LPB;
   __shared__ double P_[PW][NB];
   __shared__ double T_[CYL ? PW : 1][CYL ? 4 * (NC + 2) : 1];
@@ -777,60 +666,139 @@ pair_box_body(const double *__restrict__ src, double *__restrict__ dst,
   }
 }
 
-template <int NC, int LPB = 64>
-__global__ void __launch_bounds__(64)
-    k2_pair_box_cyl(const double *__restrict__ src, double *__restrict__ dst,
-                    const double *__restrict__ rhs, const double *__restrict__ coarse,
-                    const afh_box_meta *__restrict__ meta, const int32_t *__restrict__ ids,
-                    int n, int bsz, Coef2 cf, Bc4 g) {
-  pair_box_body<NC, LPB, true>(src, dst, rhs, coarse, meta, ids, n, bsz, cf, g);
+// ---- the 5-point stencil of a cell, three ways. A V-cycle kernel below is
+// written once and takes one of these by value.
+//   Meta   the type of the box table as init takes it: a pointer for StCyl,
+//          empty for the others (k2_gsrb and k2_parent_rhs, which need no box
+//          table themselves, carry one for StCyl only)
+//   init   by the whole workgroup before anything else
+//   apply  L phi at cell c, index x of the box image p (stencil_apply_357)
+//   relax  the cell's value after a half-sweep (stencil_gsrb_357) from its
+//          rhs r; the last operation is the variant's own: times inv_c1, times
+//          the table's inverse (the variable form, divided by v(1), is
+//          k2_gsrb_v)
+//   avg4   af_restrict_box of four fine values into cell ic of box `parent`
+struct Cell {
+  int id, i, cv;  // box id, first index, (j - 1) nc + (i - 1)
+};
+
+// StConst: the level's constant stencil (m_af_stencil.f90:421-431, 909-922)
+struct StConst {
+  Coef2 cf;
+  using Meta = NoArgs<0>;
+  __device__ void level(const Coef2 &c) { cf = c; }  // (an all-levels launch)
+  template <class M> __device__ void init(M, int, int) {}
+  __device__ double apply(const double *p, int x, int ng, Cell) const {
+    return cf.c[0] * p[x] + cf.c[1] * p[x - 1] + cf.c[2] * p[x + 1] + cf.c[3] * p[x - ng] +
+           cf.c[4] * p[x + ng];
+  }
+  __device__ double relax(double r, const double *p, int x, int ng, Cell) const {
+    return (r - cf.c[1] * p[x - 1] - cf.c[2] * p[x + 1] - cf.c[3] * p[x - ng] -
+            cf.c[4] * p[x + ng]) *
+           cf.inv_c1;
+  }
+  // 0.25 * sum(cc(i_f:i_f+1, j_f:j_f+1)): column-major section order
+  __device__ static double avg4(double v00, double v10, double v01, double v11,
+                                const afh_box_meta &, int) {
+    return 0.25 * (v00 + v10 + v01 + v11);
+  }
+};
+
+// StCyl: the constant stencil with cylindrical_gradient (m_af_stencil.f90:
+// 381-404, 863-889): the box's table (cyl_table) in 4 nc doubles of dynamic
+// LDS; the restriction with the parent's child weights (af_restrict_box with
+// geometry, m_af_restrict.f90:93-106: 0.25 (w1 sum(cc(i_f, j_f:j_f+1)) + w2
+// sum(cc(i_f+1, j_f:j_f+1))))
+struct StCyl {
+  Coef2 cf;
+  using Meta = const afh_box_meta *;
+  __device__ static double *table() {
+    extern __shared__ double cyl_T[];
+    return cyl_T;
+  }
+  __device__ void level(const Coef2 &c) { cf = c; }
+  __device__ void init(Meta meta, int id, int nc) {
+    cyl_table(table(), cf, meta[id - 1], nc);
+  }
+  __device__ double apply(const double *p, int x, int ng, Cell c) const {
+    const double *q = table() + 4 * (c.i - 1);
+    return q[0] * p[x] + q[1] * p[x - 1] + q[2] * p[x + 1] + cf.c[3] * p[x - ng] +
+           cf.c[4] * p[x + ng];
+  }
+  __device__ double relax(double r, const double *p, int x, int ng, Cell c) const {
+    const double *q = table() + 4 * (c.i - 1);
+    return (r - q[1] * p[x - 1] - q[2] * p[x + 1] - cf.c[3] * p[x - ng] -
+            cf.c[4] * p[x + ng]) *
+           q[3];
+  }
+  __device__ static double avg4(double v00, double v10, double v01, double v11,
+                                const afh_box_meta &parent, int ic) {
+    double w1, w2;
+    cyl_child_weights(parent.r_min[0], parent.dr[0], ic, w1, w2);
+    return 0.25 * (w1 * (v00 + v01) + w2 * (v10 + v11));
+  }
+};
+
+// StVar: the variable stencil of an electrode box (below; stencil_apply_357 /
+// stencil_gsrb_357, variable branch, m_af_stencil.f90:433-441, 472-475,
+// 924-934): L phi - bc_correction (its half-sweep is k2_gsrb_v)
+struct StVar {
+  const double *const *vp, *const *bp;
+  using Meta = NoArgs<0>;
+  __device__ void level(const Coef2 &) {}
+  template <class M> __device__ void init(M, int, int) {}
+  __device__ double apply(const double *p, int x, int ng, Cell c) const {
+    const double *v = vp[c.id - 1] + 5 * (size_t)c.cv, *b = bp[c.id - 1];
+    double a = v[0] * p[x] + v[1] * p[x - 1] + v[2] * p[x + 1] + v[3] * p[x - ng] +
+               v[4] * p[x + ng];
+    if (b) a = a - b[c.cv];
+    return a;
+  }
+  __device__ static double avg4(double v00, double v10, double v01, double v11,
+                                const afh_box_meta &parent, int ic) {
+    return StConst::avg4(v00, v10, v01, v11, parent, ic);
+  }
+};
+
+// one half-sweep (StConst, StCyl), one thread per cell of it
+template <class St>
+__global__ void __launch_bounds__(NT)
+    k2_gsrb(double *__restrict__ phi, const double *__restrict__ rhs,
+            const int32_t *__restrict__ ids, int nc, int bsz, St st, int redblack,
+            typename St::Meta meta) {
+  const int id = ids[blockIdx.y];
+  st.init(meta, id, nc);
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  const int half = nc >> 1;
+  if (t >= nc * half) return;
+  const int j = t / half + 1, q = t % half;
+  const int i0 = 2 - ((redblack ^ j) & 1);  // i0 = 2 - iand(ieor(redblack, j), 1)
+  const int i = i0 + 2 * q;
+  const size_t o = (size_t)(id - 1) * bsz;
+  const int x = ix2(nc + 2, i, j);
+  phi[o + x] = st.relax(rhs[o + x], phi + o, x, nc + 2, Cell{id, i, (j - 1) * nc + (i - 1)});
 }
 
-// The pair once more for a level with electrode boxes: k2_pair_box_v is
-// pair_box_body<NC, LPB, false, VAR = true> (k2_pair_box above keeps its own
-// text, k2_pair_box_cyl its code: the VAR branches are compiled out of it;
-// levels without such boxes keep launching those). vp / bp: per box id the
-// variable stencil v(5, nc, nc) and bc_correction(nc, nc), or null. A box's
-// own cells take its stencil when it has one (k2_gsrb_v: divided by v(1)),
-// the recomputed boundary cell of a same-level neighbour takes the
-// neighbour's, every other cell cf (k2_gsrb: times inv_c1). The split
-// half-sweeps leave rhs = (rhs + b) - b after each one; here rhs is read
-// only, so half-sweep s of the leg forms the value the s - 1 earlier round
-// trips would have left (pend = those before phase A) and adds b;
-// k2_rhs_roundtrip stores the leg's round trips afterwards. Bitwise k2_gsrb +
-// k2_gsrb_v + k2_gc twice.
-template <int NC, int LPB = 64>
-__global__ void __launch_bounds__(64)
-    k2_pair_box_v(const double *__restrict__ src, double *__restrict__ dst,
-                  const double *__restrict__ rhs, const double *__restrict__ coarse,
-                  const afh_box_meta *__restrict__ meta, const int32_t *__restrict__ ids,
-                  int n, int bsz, Coef2 cf, Bc4 g, const double *const *__restrict__ vp,
-                  const double *const *__restrict__ bp, int pend) {
-  pair_box_body<NC, LPB, false, true>(src, dst, rhs, coarse, meta, ids, n, bsz, cf, g, vp, bp,
-                                      pend);
-}
-
-__device__ __forceinline__ double apply5(const double *p, int x, int ng, const Coef2 &cf) {
-  return cf.c[0] * p[x] + cf.c[1] * p[x - 1] + cf.c[2] * p[x + 1] + cf.c[3] * p[x - ng] +
-         cf.c[4] * p[x + ng];
-}
-
-// tmp = rhs - L phi on the interior; with `red` the max |tmp| is folded.
+// residual_box (m_af_multigrid.f90:801-810): tmp = rhs - L phi on the
+// interior; with `red` the max |tmp| is folded.
 // lvl_c (with meta): the box's coefficients by its level -- boxes of every
 // level in one launch (they do not interact here)
+template <class St>
 __global__ void __launch_bounds__(NT)
     k2_residual(const double *__restrict__ phi, const double *__restrict__ rhs,
                 double *__restrict__ tmp, const int32_t *__restrict__ ids, int nc, int bsz,
-                Coef2 cf, unsigned long long *red, const Coef2 *__restrict__ lvl_c,
+                St st, unsigned long long *red, const Coef2 *__restrict__ lvl_c,
                 const afh_box_meta *__restrict__ meta) {
+  const int id = ids[blockIdx.y];
+  if (lvl_c) st.level(lvl_c[meta[id - 1].lvl - 1]);
+  st.init(meta, id, nc);
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   double mx = 0.0;
   if (t < nc * nc) {
-    const int i = t % nc + 1, j = t / nc + 1, ng = nc + 2;
-    const int id = ids[blockIdx.y];
+    const int i = t % nc + 1, j = t / nc + 1;
     const size_t o = (size_t)(id - 1) * bsz;
-    const int x = ix2(ng, i, j);
-    const double r = rhs[o + x] - apply5(phi + o, x, ng, lvl_c ? lvl_c[meta[id - 1].lvl - 1] : cf);
+    const int x = ix2(nc + 2, i, j);
+    const double r = rhs[o + x] - st.apply(phi + o, x, nc + 2, Cell{id, i, t});
     tmp[o + x] = r;
     mx = fabs(r);
   }
@@ -838,16 +806,19 @@ __global__ void __launch_bounds__(NT)
 }
 
 // update_coarse per child: the child's residual (not stored: the reference
-// restores the child's tmp) restricted into the parent's tmp, phi restricted
-// into the parent's phi; one thread per parent cell the child covers
+// restores the child's tmp) restricted into the parent's tmp (St::avg4), phi
+// restricted into the parent's phi (without geometry: mg_box_rstr_lpl,
+// m_af_multigrid.f90:1215-1222); one thread per parent cell the child covers
+template <class St>
 __global__ void __launch_bounds__(NT)
     k2_rstr_fas(double *__restrict__ phi, const double *__restrict__ rhs,
                 double *__restrict__ tmp, const afh_box_meta *__restrict__ meta,
-                const int32_t *__restrict__ ids, int nc, int bsz, Coef2 cf) {
+                const int32_t *__restrict__ ids, int nc, int bsz, St st) {
+  const int id = ids[blockIdx.y];
+  st.init(meta, id, nc);
   const int hnc = nc >> 1;
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= hnc * hnc) return;
-  const int id = ids[blockIdx.y];
   const afh_box_meta &m = meta[id - 1];
   const int ii = t % hnc + 1, jj = t / hnc + 1, ng = nc + 2;
   const int ic = ((m.ix[0] - 1) & 1) * hnc + ii, jc = ((m.ix[1] - 1) & 1) * hnc + jj;
@@ -855,15 +826,19 @@ __global__ void __launch_bounds__(NT)
   const size_t o = (size_t)(id - 1) * bsz, po = (size_t)(m.parent - 1) * bsz;
   const double *p = phi + o, *r = rhs + o;
   const int x00 = ix2(ng, i_f, j_f), x10 = x00 + 1, x01 = x00 + ng, x11 = x01 + 1;
-  const double r00 = r[x00] - apply5(p, x00, ng, cf), r10 = r[x10] - apply5(p, x10, ng, cf),
-               r01 = r[x01] - apply5(p, x01, ng, cf), r11 = r[x11] - apply5(p, x11, ng, cf);
-  // 0.25 * sum(cc(i_f:i_f+1, j_f:j_f+1)): column-major section order
-  tmp[po + ix2(ng, ic, jc)] = 0.25 * (r00 + r10 + r01 + r11);
+  const int c00 = (j_f - 1) * nc + (i_f - 1);
+  const double r00 = r[x00] - st.apply(p, x00, ng, Cell{id, i_f, c00}),
+               r10 = r[x10] - st.apply(p, x10, ng, Cell{id, i_f + 1, c00 + 1}),
+               r01 = r[x01] - st.apply(p, x01, ng, Cell{id, i_f, c00 + nc}),
+               r11 = r[x11] - st.apply(p, x11, ng, Cell{id, i_f + 1, c00 + nc + 1});
+  tmp[po + ix2(ng, ic, jc)] = St::avg4(r00, r10, r01, r11, meta[m.parent - 1], ic);
   phi[po + ix2(ng, ic, jc)] = 0.25 * (p[x00] + p[x10] + p[x01] + p[x11]);
 }
 
-// af_restrict_box of variable v (children -> parent), one thread per parent
-// cell of one child; ids = the children
+// af_restrict_box of variable v (children -> parent; St: StConst, or StCyl
+// for the restriction with geometry), one thread per parent cell of one
+// child; ids = the children
+template <class St>
 __global__ void __launch_bounds__(NT)
     k2_restrict(double *__restrict__ v, const afh_box_meta *__restrict__ meta,
                 const int32_t *__restrict__ ids, int nc, int bsz) {
@@ -877,113 +852,19 @@ __global__ void __launch_bounds__(NT)
   const double *c = v + (size_t)(id - 1) * bsz;
   const int x00 = ix2(ng, 2 * ii - 1, 2 * jj - 1);
   v[(size_t)(m.parent - 1) * bsz + ix2(ng, ic, jc)] =
-      0.25 * (c[x00] + c[x00 + 1] + c[x00 + ng] + c[x00 + ng + 1]);
+      St::avg4(c[x00], c[x00 + 1], c[x00 + ng], c[x00 + ng + 1], meta[m.parent - 1], ic);
 }
 
 // parents of the coarse level: rhs = L phi (interior), then rhs = rhs + tmp
 // and (with `copy`) tmp = phi over the whole block (af_box_add_cc /
 // af_box_copy_cc use DTIMES(:))
+template <class St>
 __global__ void __launch_bounds__(NT)
     k2_parent_rhs(const double *__restrict__ phi, double *__restrict__ rhs,
                   double *__restrict__ tmp, const int32_t *__restrict__ ids, int nc, int bsz,
-                  Coef2 cf, int copy) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  const int ng = nc + 2;
-  if (t >= ng * ng) return;
-  const size_t o = (size_t)(ids[blockIdx.y] - 1) * bsz;
-  const int i = t % ng, j = t / ng;
-  double r = rhs[o + t];
-  if (i >= 1 && i <= nc && j >= 1 && j <= nc) r = apply5(phi + o, t, ng, cf);
-  rhs[o + t] = r + tmp[o + t];
-  if (copy) tmp[o + t] = phi[o + t];
-}
-
-// ---- the cylindrical forms of the four kernels above (4 nc doubles of
-// dynamic LDS each: the box's coefficient table, or its parent's child
-// weights)
-__global__ void __launch_bounds__(NT)
-    k2_residual_cyl(const double *__restrict__ phi, const double *__restrict__ rhs,
-                    double *__restrict__ tmp, const int32_t *__restrict__ ids, int nc, int bsz,
-                    Coef2 cf, unsigned long long *red, const Coef2 *__restrict__ lvl_c,
-                    const afh_box_meta *__restrict__ meta) {
-  extern __shared__ double cyl_T[];
+                  St st, int copy, typename St::Meta meta) {
   const int id = ids[blockIdx.y];
-  const afh_box_meta &m = meta[id - 1];
-  const Coef2 c = lvl_c ? lvl_c[m.lvl - 1] : cf;
-  cyl_table(cyl_T, c, m, nc);
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  double mx = 0.0;
-  if (t < nc * nc) {
-    const int i = t % nc + 1, j = t / nc + 1, ng = nc + 2;
-    const size_t o = (size_t)(id - 1) * bsz;
-    const int x = ix2(ng, i, j);
-    const double r = rhs[o + x] - apply5_cyl(phi + o, x, ng, cyl_T + 4 * (i - 1), c);
-    tmp[o + x] = r;
-    mx = fabs(r);
-  }
-  if (red) block_fold<true>(mx, red);
-}
-
-// update_coarse per child in af_cyl: the residual restricted with the
-// parent's child weights (af_restrict_box with geometry, m_af_restrict.f90:
-// 93-106: 0.25 (w1 sum(cc(i_f, j_f:j_f+1)) + w2 sum(cc(i_f+1, j_f:j_f+1)))),
-// phi without (mg_box_rstr_lpl, m_af_multigrid.f90:1215-1222)
-__global__ void __launch_bounds__(NT)
-    k2_rstr_fas_cyl(double *__restrict__ phi, const double *__restrict__ rhs,
-                    double *__restrict__ tmp, const afh_box_meta *__restrict__ meta,
-                    const int32_t *__restrict__ ids, int nc, int bsz, Coef2 cf) {
-  extern __shared__ double cyl_T[];
-  const int id = ids[blockIdx.y];
-  const afh_box_meta &m = meta[id - 1];
-  cyl_table(cyl_T, cf, m, nc);
-  const int hnc = nc >> 1;
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= hnc * hnc) return;
-  const int ii = t % hnc + 1, jj = t / hnc + 1, ng = nc + 2;
-  const int ic = ((m.ix[0] - 1) & 1) * hnc + ii, jc = ((m.ix[1] - 1) & 1) * hnc + jj;
-  const int i_f = 2 * ii - 1, j_f = 2 * jj - 1;
-  const size_t o = (size_t)(id - 1) * bsz, po = (size_t)(m.parent - 1) * bsz;
-  const double *p = phi + o, *r = rhs + o;
-  const int x00 = ix2(ng, i_f, j_f), x10 = x00 + 1, x01 = x00 + ng, x11 = x01 + 1;
-  const double *q0 = cyl_T + 4 * (i_f - 1), *q1 = q0 + 4;
-  const double r00 = r[x00] - apply5_cyl(p, x00, ng, q0, cf),
-               r10 = r[x10] - apply5_cyl(p, x10, ng, q1, cf),
-               r01 = r[x01] - apply5_cyl(p, x01, ng, q0, cf),
-               r11 = r[x11] - apply5_cyl(p, x11, ng, q1, cf);
-  const afh_box_meta &mp = meta[m.parent - 1];
-  double w1, w2;
-  cyl_child_weights(mp.r_min[0], mp.dr[0], ic, w1, w2);
-  tmp[po + ix2(ng, ic, jc)] = 0.25 * (w1 * (r00 + r01) + w2 * (r10 + r11));
-  phi[po + ix2(ng, ic, jc)] = 0.25 * (p[x00] + p[x10] + p[x01] + p[x11]);
-}
-
-// af_restrict_box with geometry in af_cyl
-__global__ void __launch_bounds__(NT)
-    k2_restrict_cyl(double *__restrict__ v, const afh_box_meta *__restrict__ meta,
-                    const int32_t *__restrict__ ids, int nc, int bsz) {
-  const int hnc = nc >> 1;
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= hnc * hnc) return;
-  const int id = ids[blockIdx.y];
-  const afh_box_meta &m = meta[id - 1];
-  const int ii = t % hnc + 1, jj = t / hnc + 1, ng = nc + 2;
-  const int ic = ((m.ix[0] - 1) & 1) * hnc + ii, jc = ((m.ix[1] - 1) & 1) * hnc + jj;
-  const double *c = v + (size_t)(id - 1) * bsz;
-  const int x00 = ix2(ng, 2 * ii - 1, 2 * jj - 1);
-  const afh_box_meta &mp = meta[m.parent - 1];
-  double w1, w2;
-  cyl_child_weights(mp.r_min[0], mp.dr[0], ic, w1, w2);
-  v[(size_t)(m.parent - 1) * bsz + ix2(ng, ic, jc)] =
-      0.25 * (w1 * (c[x00] + c[x00 + ng]) + w2 * (c[x00 + 1] + c[x00 + ng + 1]));
-}
-
-__global__ void __launch_bounds__(NT)
-    k2_parent_rhs_cyl(const double *__restrict__ phi, double *__restrict__ rhs,
-                      double *__restrict__ tmp, const afh_box_meta *__restrict__ meta,
-                      const int32_t *__restrict__ ids, int nc, int bsz, Coef2 cf, int copy) {
-  extern __shared__ double cyl_T[];
-  const int id = ids[blockIdx.y];
-  cyl_table(cyl_T, cf, meta[id - 1], nc);
+  st.init(meta, id, nc);
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   const int ng = nc + 2;
   if (t >= ng * ng) return;
@@ -991,7 +872,7 @@ __global__ void __launch_bounds__(NT)
   const int i = t % ng, j = t / ng;
   double r = rhs[o + t];
   if (i >= 1 && i <= nc && j >= 1 && j <= nc)
-    r = apply5_cyl(phi + o, t, ng, cyl_T + 4 * (i - 1), cf);
+    r = st.apply(phi + o, t, ng, Cell{id, i, (j - 1) * nc + (i - 1)});
   rhs[o + t] = r + tmp[o + t];
   if (copy) tmp[o + t] = phi[o + t];
 }
@@ -1002,15 +883,13 @@ __global__ void __launch_bounds__(NT)
 // coefficients fastest as afivo stores them, and bc_correction(nc, nc) (f
 // times the electrode potential, mg_set_operators_lvl 1156-1160); vp / bp
 // index them by box id (bp null: no correction). These kernels run on the
-// lists of such boxes only, the constant kernels on the rest of each level:
-// a tree without electrodes launches none of them.
-__device__ __forceinline__ double apply5v(const double *p, int x, int ng, const double *v) {
-  return v[0] * p[x] + v[1] * p[x - 1] + v[2] * p[x + 1] + v[3] * p[x - ng] + v[4] * p[x + ng];
-}
+// lists of such boxes only (the V-cycle kernels above with StVar), StConst on
+// the rest of each level: a tree without electrodes launches none of them.
 
 // stencil_gsrb_357, variable branch (m_af_stencil.f90:838-841, 924-934,
 // 975-978): rhs + bc_correction on every cell, the cells of the half sweep
-// divided by v(1), rhs - bc_correction; one thread per cell
+// divided by v(1), rhs - bc_correction; one thread per cell (every cell's rhs
+// makes the round trip: not k2_gsrb's thread map)
 __global__ void __launch_bounds__(NT)
     k2_gsrb_v(double *__restrict__ phi, double *__restrict__ rhs,
               const int32_t *__restrict__ ids, int nc, int bsz,
@@ -1034,7 +913,7 @@ __global__ void __launch_bounds__(NT)
 }
 
 // The rhs round trips (rhs + bc_correction - bc_correction) of the n
-// half-sweeps a leg of fused variable pairs did (k2_pair_box_v), in the order
+// half-sweeps a leg of fused variable pairs did (k2_pair_box, VAR), in the order
 // k2_gsrb_v applies them
 __global__ void __launch_bounds__(NT)
     k2_rhs_roundtrip(double *__restrict__ rhs, const int32_t *__restrict__ ids, int nc, int bsz,
@@ -1048,82 +927,6 @@ __global__ void __launch_bounds__(NT)
   double v = *r;
   for (int q = 0; q < n; q++) v = (v + b[t]) - b[t];
   *r = v;
-}
-
-// residual_box with the variable stencil: tmp = rhs - (L phi - bc_correction)
-// (stencil_apply_357, m_af_stencil.f90:433-441, 472-475); with `red` the max
-// |tmp| is folded
-__global__ void __launch_bounds__(NT)
-    k2_residual_v(const double *__restrict__ phi, const double *__restrict__ rhs,
-                  double *__restrict__ tmp, const int32_t *__restrict__ ids, int nc, int bsz,
-                  const double *const *__restrict__ vp, const double *const *__restrict__ bp,
-                  unsigned long long *red) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  double mx = 0.0;
-  if (t < nc * nc) {
-    const int id = ids[blockIdx.y];
-    const int i = t % nc + 1, j = t / nc + 1, ng = nc + 2;
-    const size_t o = (size_t)(id - 1) * bsz;
-    const int x = ix2(ng, i, j);
-    double a = apply5v(phi + o, x, ng, vp[id - 1] + 5 * (size_t)t);
-    if (bp[id - 1]) a = a - bp[id - 1][t];
-    const double r = rhs[o + x] - a;
-    tmp[o + x] = r;
-    mx = fabs(r);
-  }
-  if (red) block_fold<true>(mx, red);
-}
-
-// k2_rstr_fas for children with a variable stencil
-__global__ void __launch_bounds__(NT)
-    k2_rstr_fas_v(double *__restrict__ phi, const double *__restrict__ rhs,
-                  double *__restrict__ tmp, const afh_box_meta *__restrict__ meta,
-                  const int32_t *__restrict__ ids, int nc, int bsz,
-                  const double *const *__restrict__ vp, const double *const *__restrict__ bp) {
-  const int hnc = nc >> 1;
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= hnc * hnc) return;
-  const int id = ids[blockIdx.y];
-  const afh_box_meta &m = meta[id - 1];
-  const int ii = t % hnc + 1, jj = t / hnc + 1, ng = nc + 2;
-  const int ic = ((m.ix[0] - 1) & 1) * hnc + ii, jc = ((m.ix[1] - 1) & 1) * hnc + jj;
-  const int i_f = 2 * ii - 1, j_f = 2 * jj - 1;
-  const size_t o = (size_t)(id - 1) * bsz, po = (size_t)(m.parent - 1) * bsz;
-  const double *p = phi + o, *r = rhs + o, *v = vp[id - 1], *b = bp[id - 1];
-  double res[4], ph[4];
-#pragma unroll
-  for (int q = 0; q < 4; q++) {
-    const int ci = i_f + (q & 1), cj = j_f + (q >> 1);
-    const int x = ix2(ng, ci, cj), cv = (cj - 1) * nc + (ci - 1);
-    double a = apply5v(p, x, ng, v + 5 * (size_t)cv);
-    if (b) a = a - b[cv];
-    res[q] = r[x] - a;
-    ph[q] = p[x];
-  }
-  tmp[po + ix2(ng, ic, jc)] = 0.25 * (res[0] + res[1] + res[2] + res[3]);
-  phi[po + ix2(ng, ic, jc)] = 0.25 * (ph[0] + ph[1] + ph[2] + ph[3]);
-}
-
-// k2_parent_rhs for parents with a variable stencil
-__global__ void __launch_bounds__(NT)
-    k2_parent_rhs_v(const double *__restrict__ phi, double *__restrict__ rhs,
-                    double *__restrict__ tmp, const int32_t *__restrict__ ids, int nc, int bsz,
-                    const double *const *__restrict__ vp, const double *const *__restrict__ bp,
-                    int copy) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  const int ng = nc + 2;
-  if (t >= ng * ng) return;
-  const int id = ids[blockIdx.y];
-  const size_t o = (size_t)(id - 1) * bsz;
-  const int i = t % ng, j = t / ng;
-  double r = rhs[o + t];
-  if (i >= 1 && i <= nc && j >= 1 && j <= nc) {
-    const int cv = (j - 1) * nc + (i - 1);
-    r = apply5v(phi + o, t, ng, vp[id - 1] + 5 * (size_t)cv);
-    if (bp[id - 1]) r = r - bp[id - 1][cv];
-  }
-  rhs[o + t] = r + tmp[o + t];
-  if (copy) tmp[o + t] = phi[o + t];
 }
 
 // mg_box_lpllsf_gradient, NDIM == 2 (m_af_multigrid.f90:2068-2087), on
@@ -1805,93 +1608,35 @@ __device__ __forceinline__ double rate_of(const UpdArgs &A, const DevReaction &R
 // step), then the flux divergence of the electrons (flux species). NS: the
 // species count when it is a compile-time case (the per-cell arrays then stay
 // in registers; wave-uniform indices use VGPR index mode), MAXS for any count
-// (A.ns; the arrays in scratch)
-template <int NS>
-__global__ void __launch_bounds__(NT)
-    k2_update(UpdArgs A, const int32_t *__restrict__ ids, const afh_box_meta *__restrict__ meta,
-              int nc, int bsz, int fsz, unsigned long long *red) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  double cmin = 1e100;
-  const int ns = NS == MAXS ? A.ns : NS;
-  if (t < nc * nc) {
-    const int id = ids[blockIdx.y];
-    const int i = t % nc + 1, j = t / nc + 1, ng = nc + 2, nf = nc + 1;
-    const size_t x = (size_t)(id - 1) * bsz + ix2(ng, i, j);
-    double y[NS], dens[NS], der[NS];
-#pragma unroll
-    for (int s = 0; s < ns; s++) {
-      double tmp = 0.0;
-      for (int q = 0; q < A.n_prev; q++) tmp = tmp + A.w_prev[q] * A.prev[s][q][x];
-      y[s] = tmp;
-      const double v = A.der[s][x];
-      dens[s] = v > 0.0 ? v : 0.0;
-      der[s] = 0.0;
-    }
-    const double field = 1e21 * A.inv_N * A.E[x];
-    for (int r = 0; r < A.nr; r++) {
-      const DevReaction &R = A.reac[r];
-      double rate = rate_of(A, R, field);
-      double prod = 1.0;
-      for (int q = 0; q < R.n_in; q++) prod = prod * dens[R.ix_in[q] - 1];
-      rate = rate * prod;
-      for (int q = 0; q < R.n_in; q++) der[R.ix_in[q] - 1] = der[R.ix_in[q] - 1] - rate;
-      for (int q = 0; q < R.n_out; q++)
-        der[R.ix_out[q] - 1] = der[R.ix_out[q] - 1] + rate * R.mult_out[q];
-    }
-    if (A.last_step) {
-      const double eps = 1e-100;
-#pragma unroll
-      for (int s = 0; s < ns; s++) {
-        double a, b;
-        if (A.dt_chemistry_nmin > 0) {
-          a = dens[s] + A.dt_chemistry_nmin;
-          b = fabs(der[s]);
-          b = b > eps ? b : eps;
-        } else {
-          a = dens[s] > eps ? dens[s] : eps;
-          b = -der[s] > eps ? -der[s] : eps;
-        }
-        cmin = fmin(cmin, a / b);
-      }
-    }
-#pragma unroll
-    for (int s = 0; s < ns; s++) y[s] = y[s] + A.dt * der[s];
-    const double *F = A.F + (size_t)(id - 1) * fsz;
-    const int f0 = (j - 1) * nf + (i - 1), d2 = nf * nf;
-    const double dtx = A.dt / meta[id - 1].dr[0], dty = A.dt / meta[id - 1].dr[1];
-    const int e = A.e_index;
-    y[e] = y[e] + dtx * (F[f0] - F[f0 + 1]) + dty * (F[d2 + f0] - F[d2 + f0 + nf]);
-#pragma unroll
-    for (int s = 0; s < ns; s++) A.out[s][x] = y[s];
-  }
-  if (A.last_step) block_fold<false>(cmin, red);
-}
-
-// The update once more for a cylindrical tree (k2_update_cyl, CYL = true the
-// only instantiation; k2_update above keeps its own text): the r-fluxes times
-// af_cyl_flux_factors inside the divergence (m_af_flux_schemes.f90:395-406)
-// PHOTO (k2_update_photo, k2_update_cyl_photo; a fluid with i_photo > 0): the
-// photoionization rate P.photo added to the derivative of the electrons and
-// of species slot P.s after the chemistry limit (m_fluid.f90:435-440). The
-// kernels of a fluid without it take no such argument and keep their code.
+// (A.ns; the arrays in scratch). One kernel, k2_update<NS, CYL, PHOTO, MASK,
+// IONS>; a feature that is off is compiled out and its argument block is
+// empty (UpdOpt).
+//
+// CYL (a cylindrical tree): the r-fluxes times af_cyl_flux_factors inside the
+// divergence (m_af_flux_schemes.f90:395-406)
+//
+// PHOTO (a fluid with i_photo > 0): the photoionization rate P.photo added to
+// the derivative of the electrons and of species slot P.s after the chemistry
+// limit (m_fluid.f90:435-440)
 struct PhotoArgs {
   const double *photo;
   int s;
 };
 
-// MASK (k2_update_mask, k2_update_photo_mask; afh_fluid_set_update_mask):
-// set_box_mask's electrode part (src/m_fluid.f90:469-483). A cell whose level
+// MASK (afh_fluid_set_update_mask): set_box_mask's electrode part
+// (src/m_fluid.f90:469-483). A cell whose level
 // set M.lsf is <= 0 keeps the weighted sum of the previous states: no
 // chemistry source, no photoionization, no flux divergence
 // (m_af_flux_schemes.f90:408-416 with the mask); a box with no other cell
 // (M.stat[id - 1] = 0, k2_mask_status) adds no chemistry limit either
-// (add_source_terms returns before it, m_fluid.f90:332).
+// (add_source_terms returns before it, m_fluid.f90:332). Not built together
+// with CYL (update() refuses it).
 struct MaskArgs {
   const double *lsf;
   const uint8_t *stat;
 };
 
-// IONS (k2_update_ions; a fluid with n_ions > 0): every mobile ion adds the
+// IONS (a fluid with n_ions > 0): every mobile ion adds the
 // divergence of its own face flux I.F[q] to its species slot I.s[q]
 // (flux_update_densities over all flux variables, m_af_flux_schemes.f90:
 // 386-417), after the electrons and in the same expression; a masked cell
@@ -1902,12 +1647,32 @@ struct IonUpdArgs {
   const double *F[AFH_MAX_IONS];
 };
 
-template <int NS, bool CYL, bool PHOTO = false, bool MASK = false, bool IONS = false>
-__device__ __forceinline__ void
-update_body(UpdArgs A, const int32_t *__restrict__ ids,
-            const afh_box_meta *__restrict__ meta, int nc, int bsz, int fsz,
-            unsigned long long *red, PhotoArgs P = PhotoArgs{nullptr, 0},
-            MaskArgs M = MaskArgs{nullptr, nullptr}, IonUpdArgs I = IonUpdArgs{0, {}, {}}) {
+// f(std::true_type or std::false_type) for the run-time flag on
+template <class F> inline void with_flag(bool on, F &&f) {
+  if (on) f(std::true_type{});
+  else f(std::false_type{});
+}
+
+// f(Int<NS>) for the run-time species count ns: NS = ns for 1 .. 12, else
+// MAXS
+template <int N = 1, class F> inline void with_species_count(int ns, F &&f) {
+  if constexpr (N > 12) f(Int<MAXS>{});
+  else if (ns == N) f(Int<N>{});
+  else with_species_count<N + 1>(ns, f);
+}
+
+template <bool PHOTO, bool MASK, bool IONS>
+struct UpdOpt : ArgsIf<PHOTO, PhotoArgs, 0>, ArgsIf<MASK, MaskArgs, 1>,
+                ArgsIf<IONS, IonUpdArgs, 2> {};
+
+template <int NS, bool CYL, bool PHOTO, bool MASK, bool IONS>
+__global__ void __launch_bounds__(NT)
+    k2_update(UpdArgs A, const int32_t *__restrict__ ids, const afh_box_meta *__restrict__ meta,
+              int nc, int bsz, int fsz, UpdOpt<PHOTO, MASK, IONS> O, unsigned long long *red) {
+  const ArgsIf<PHOTO, PhotoArgs, 0> &P = O;
+  const ArgsIf<MASK, MaskArgs, 1> &M = O;
+  const ArgsIf<IONS, IonUpdArgs, 2> &I = O;
+  static_assert(!(CYL && MASK), "the update mask in cylindrical coordinates is not built");
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   double cmin = 1e100;
   const int ns = NS == MAXS ? A.ns : NS;
@@ -1916,8 +1681,8 @@ update_body(UpdArgs A, const int32_t *__restrict__ ids,
     const int i = t % nc + 1, j = t / nc + 1, ng = nc + 2, nf = nc + 1;
     const size_t x = (size_t)(id - 1) * bsz + ix2(ng, i, j);
     // `where (lsf <= 0) mask = .false.` (a NaN stays true)
-    const bool upd = !MASK || !(M.lsf[x] <= 0.0);
-    const bool src = !MASK || M.stat[id - 1] != 0;
+    bool upd = true, src = true;
+    if constexpr (MASK) upd = !(M.lsf[x] <= 0.0), src = M.stat[id - 1] != 0;
     double y[NS], dens[NS], der[NS];
 #pragma unroll
     for (int s = 0; s < ns; s++) {
@@ -1955,10 +1720,12 @@ update_body(UpdArgs A, const int32_t *__restrict__ ids,
         cmin = fmin(cmin, a / b);
       }
     }
-    if (PHOTO && upd) {
-      const double pho = P.photo[x];
-      der[A.e_index] = der[A.e_index] + pho;
-      der[P.s] = der[P.s] + pho;
+    if constexpr (PHOTO) {
+      if (upd) {
+        const double pho = P.photo[x];
+        der[A.e_index] = der[A.e_index] + pho;
+        der[P.s] = der[P.s] + pho;
+      }
     }
     if (upd) {
 #pragma unroll
@@ -1978,73 +1745,25 @@ update_body(UpdArgs A, const int32_t *__restrict__ ids,
     } else {
       y[e] = y[e] + dtx * (F[f0] - F[f0 + 1]) + dty * (F[d2 + f0] - F[d2 + f0 + nf]);
     }
-    if (IONS && !(MASK && !upd)) {
-      double rf1 = 1.0, rf2 = 1.0;
-      if (CYL) cyl_flux_factors(meta[id - 1].r_min[0], meta[id - 1].dr[0], i, rf1, rf2);
-      for (int q = 0; q < I.n; q++) {
-        const double *Fq = I.F[q] + (size_t)(id - 1) * fsz;
-        const int s = I.s[q];
-        if (CYL)
-          y[s] = y[s] + dtx * (rf1 * Fq[f0] - rf2 * Fq[f0 + 1]) +
-                 dty * (Fq[d2 + f0] - Fq[d2 + f0 + nf]);
-        else
-          y[s] = y[s] + dtx * (Fq[f0] - Fq[f0 + 1]) + dty * (Fq[d2 + f0] - Fq[d2 + f0 + nf]);
+    if constexpr (IONS) {
+      if (!(MASK && !upd)) {
+        double rf1 = 1.0, rf2 = 1.0;
+        if (CYL) cyl_flux_factors(meta[id - 1].r_min[0], meta[id - 1].dr[0], i, rf1, rf2);
+        for (int q = 0; q < I.n; q++) {
+          const double *Fq = I.F[q] + (size_t)(id - 1) * fsz;
+          const int s = I.s[q];
+          if (CYL)
+            y[s] = y[s] + dtx * (rf1 * Fq[f0] - rf2 * Fq[f0 + 1]) +
+                   dty * (Fq[d2 + f0] - Fq[d2 + f0 + nf]);
+          else
+            y[s] = y[s] + dtx * (Fq[f0] - Fq[f0 + 1]) + dty * (Fq[d2 + f0] - Fq[d2 + f0 + nf]);
+        }
       }
     }
 #pragma unroll
     for (int s = 0; s < ns; s++) A.out[s][x] = y[s];
   }
   if (A.last_step) block_fold<false>(cmin, red);
-}
-
-// the update of a fluid with mobile ions: one entry for the combinations the
-// body serves (Cartesian / cylindrical, photoionization, the update mask)
-template <int NS, bool CYL, bool PHOTO, bool MASK>
-__global__ void __launch_bounds__(NT)
-    k2_update_ions(UpdArgs A, const int32_t *__restrict__ ids,
-                   const afh_box_meta *__restrict__ meta, int nc, int bsz, int fsz,
-                   unsigned long long *red, PhotoArgs P, MaskArgs M, IonUpdArgs I) {
-  update_body<NS, CYL, PHOTO, MASK, true>(A, ids, meta, nc, bsz, fsz, red, P, M, I);
-}
-
-template <int NS>
-__global__ void __launch_bounds__(NT)
-    k2_update_cyl(UpdArgs A, const int32_t *__restrict__ ids,
-                  const afh_box_meta *__restrict__ meta, int nc, int bsz, int fsz,
-                  unsigned long long *red) {
-  update_body<NS, true>(A, ids, meta, nc, bsz, fsz, red);
-}
-
-template <int NS>
-__global__ void __launch_bounds__(NT)
-    k2_update_photo(UpdArgs A, const int32_t *__restrict__ ids,
-                    const afh_box_meta *__restrict__ meta, int nc, int bsz, int fsz,
-                    unsigned long long *red, PhotoArgs P) {
-  update_body<NS, false, true>(A, ids, meta, nc, bsz, fsz, red, P);
-}
-
-template <int NS>
-__global__ void __launch_bounds__(NT)
-    k2_update_cyl_photo(UpdArgs A, const int32_t *__restrict__ ids,
-                        const afh_box_meta *__restrict__ meta, int nc, int bsz, int fsz,
-                        unsigned long long *red, PhotoArgs P) {
-  update_body<NS, true, true>(A, ids, meta, nc, bsz, fsz, red, P);
-}
-
-template <int NS>
-__global__ void __launch_bounds__(NT)
-    k2_update_mask(UpdArgs A, const int32_t *__restrict__ ids,
-                   const afh_box_meta *__restrict__ meta, int nc, int bsz, int fsz,
-                   unsigned long long *red, MaskArgs M) {
-  update_body<NS, false, false, true>(A, ids, meta, nc, bsz, fsz, red, PhotoArgs{nullptr, 0}, M);
-}
-
-template <int NS>
-__global__ void __launch_bounds__(NT)
-    k2_update_photo_mask(UpdArgs A, const int32_t *__restrict__ ids,
-                         const afh_box_meta *__restrict__ meta, int nc, int bsz, int fsz,
-                         unsigned long long *red, PhotoArgs P, MaskArgs M) {
-  update_body<NS, false, true, true>(A, ids, meta, nc, bsz, fsz, red, P, M);
 }
 
 // per leaf box whether set_box_mask leaves any cell to update (any(mask));
@@ -2453,14 +2172,14 @@ static int32_t check_iv(afh_tree *t, int iv, const char *what) {
 static void restrict_boxes(afh_tree *t, double *v, const int32_t *ids, int n, bool geometry) {
   const int w = t->nc * t->nc / 4;
   if (t->cyl() && geometry)
-    hipLaunchKernelGGL(k2_restrict_cyl, grid2(w, n), blk2(w), 0, t->stream, v, t->d_boxes, ids,
-                       t->nc, t->bsz);
+    hipLaunchKernelGGL(k2_restrict<StCyl>, grid2(w, n), blk2(w), 0, t->stream, v, t->d_boxes,
+                       ids, t->nc, t->bsz);
   else
-    hipLaunchKernelGGL(k2_restrict, grid2(w, n), blk2(w), 0, t->stream, v, t->d_boxes, ids,
-                       t->nc, t->bsz);
+    hipLaunchKernelGGL(k2_restrict<StConst>, grid2(w, n), blk2(w), 0, t->stream, v, t->d_boxes,
+                       ids, t->nc, t->bsz);
 }
 
-// dynamic LDS of the *_cyl kernels' coefficient table
+// dynamic LDS of StCyl's coefficient table
 static inline size_t cyl_lds(const afh_tree *t) { return sizeof(double) * 4 * t->nc; }
 
 }  // namespace afh2
@@ -2918,6 +2637,21 @@ static const LevelList &cst(const afh_mg *mg, const LevelList &all, const LevelL
   return mg->any_var ? c : all;
 }
 
+// the box table as St's init takes it (St::Meta)
+template <class St> static typename St::Meta stencil_meta(const afh_tree *t) {
+  if constexpr (std::is_pointer_v<typename St::Meta>) return t->d_boxes;
+  else return {};
+}
+
+// f(stencil policy, its dynamic LDS) for boxes of level lvl: StVar for a list
+// of electrode boxes (var), else StCyl on a cylindrical tree, else StConst
+template <class F> static void with_stencil(const afh_mg *mg, int lvl, bool var, F &&f) {
+  const afh_tree *t = mg->t;
+  if (var) f(StVar{mg->d_vp, mg->d_bp}, (size_t)0);
+  else if (t->cyl()) f(StCyl{mg->lvl_c[lvl - 1]}, cyl_lds(t));
+  else f(StConst{mg->lvl_c[lvl - 1]}, (size_t)0);
+}
+
 // AFH_COARSE_PFMG: the folded level-1 operator (stencil_handle_boundaries,
 // the 3-D library's pf_prepare with NDIM = 2), the hierarchy when the
 // boundary types change, then k2_cs_pfmg
@@ -3077,6 +2811,35 @@ static int32_t solve_coarse(afh_mg *mg) {
   return gc_lvl(t, 1, mg->d.i_phi, true);
 }
 
+// one fused pair src -> dst on level lvl: k2_pair_box for the box size
+// (several boxes per wave: four 4^2, two 8^2), the tree's coordinates and
+// whether the level has electrode boxes (var; pend: the leg's half-sweeps
+// before this pair)
+static void pair_launch(afh_mg *mg, int lvl, bool var, const double *src, double *dst,
+                        int pend) {
+  afh_tree *t = mg->t;
+  const int n = t->ids.n(lvl);
+  auto go = [&](auto nc_, auto lpb_, auto cyl_, auto var_) {
+    constexpr int NC = decltype(nc_)::value, LPB = decltype(lpb_)::value;
+    constexpr bool C = decltype(cyl_)::value, VA = decltype(var_)::value;
+    PairBc<VA> gv;
+    static_cast<Bc4 &>(gv) = t->bc4(mg->d.i_phi);
+    if constexpr (VA) static_cast<PairVarArgs &>(gv) = PairVarArgs{mg->d_vp, mg->d_bp, pend};
+    hipLaunchKernelGGL((k2_pair_box<NC, LPB, C, VA>), dim3((n + 64 / LPB - 1) / (64 / LPB)),
+                       dim3(64), 0, t->stream, src, dst, t->ccv(mg->d.i_rhs),
+                       t->ccv(mg->d.i_phi), t->d_boxes, t->ids.at(lvl), n, t->bsz,
+                       mg->lvl_c[lvl - 1], gv);
+  };
+  auto size = [&](auto cyl_, auto var_) {
+    if (t->nc == 4) go(Int<4>{}, Int<16>{}, cyl_, var_);
+    else if (t->nc == 8) go(Int<8>{}, Int<32>{}, cyl_, var_);
+    else go(Int<16>{}, Int<64>{}, cyl_, var_);
+  };
+  if (var) size(std::false_type{}, std::true_type{});
+  else if (t->cyl()) size(std::true_type{}, std::false_type{});
+  else size(std::false_type{}, std::false_type{});
+}
+
 // gsrb_boxes (m_af_multigrid.f90:648-687): 2 n_cycle half sweeps, each
 // followed by the level fill (corners after the last sweep of the up leg)
 // skip_corners: the up leg's corner pass is left to correct_children of the
@@ -3088,76 +2851,26 @@ static int32_t gsrb_boxes(afh_mg *mg, int lvl, bool up, bool skip_corners = fals
   // a level with electrode boxes: the pair's variable form, or the split
   // half-sweeps (AFH_PAIR2D=0)
   const bool var = mg->any_var && mg->lvl_var[lvl - 1];
-  if (mg->pair && n && var) {
-    double *phi = t->ccv(mg->d.i_phi);
-    const double *rh = t->ccv(mg->d.i_rhs);
-    const int32_t *ids = t->ids.at(lvl);
-    const Coef2 cf = mg->lvl_c[lvl - 1];
-    const Bc4 g = t->bc4(mg->d.i_phi);
-    for (int p = 0; p < nc_; p++) {
-      const double *src = (p & 1) ? mg->alt : phi;
-      double *dst = (p & 1) ? phi : mg->alt;
-      if (t->nc == 4)
-        hipLaunchKernelGGL((k2_pair_box_v<4, 16>), dim3((n + 3) / 4), dim3(64), 0, t->stream,
-                           src, dst, rh, phi, t->d_boxes, ids, n, t->bsz, cf, g, mg->d_vp,
-                           mg->d_bp, 2 * p);
-      else if (t->nc == 8)
-        hipLaunchKernelGGL((k2_pair_box_v<8, 32>), dim3((n + 1) / 2), dim3(64), 0, t->stream,
-                           src, dst, rh, phi, t->d_boxes, ids, n, t->bsz, cf, g, mg->d_vp,
-                           mg->d_bp, 2 * p);
-      else
-        hipLaunchKernelGGL(k2_pair_box_v<16>, dim3(n), dim3(64), 0, t->stream, src, dst, rh,
-                           phi, t->d_boxes, ids, n, t->bsz, cf, g, mg->d_vp, mg->d_bp, 2 * p);
-      H2_LAUNCH("k2_pair_box_v");
-    }
-    const int nv = mg->ids_v.n(lvl);
-    hipLaunchKernelGGL(k2_rhs_roundtrip, grid2(t->nc * t->nc, nv), blk2(t->nc * t->nc), 0,
-                       t->stream, t->ccv(mg->d.i_rhs), mg->ids_v.at(lvl), t->nc, t->bsz,
-                       mg->d_bp, 2 * nc_);
-    H2_LAUNCH("k2_rhs_roundtrip");
-    if (up && !skip_corners) {
-      hipLaunchKernelGGL(k2_corners, dim3((4 * n + NT - 1) / NT), dim3(NT), 0, t->stream,
-                         phi, t->d_boxes, t->ids.at(lvl), n, t->nc, t->bsz);
-      H2_LAUNCH("k2_corners");
-    }
-    return AFH_OK;
-  }
-  if (mg->pair && n && !var) {
+  if (mg->pair && n) {
     // n_cycle fused pairs, phi -> alt -> phi (n_cycle even); the corners of
     // the up leg's last fill after them
     double *phi = t->ccv(mg->d.i_phi);
     for (int p = 0; p < nc_; p++) {
-      const double *src = (p & 1) ? mg->alt : phi;
-      double *dst = (p & 1) ? phi : mg->alt;
-      const Coef2 cf = mg->lvl_c[lvl - 1];
-      const Bc4 g = t->bc4(mg->d.i_phi);
-      // timed on levels of >= 256 boxes, as the split half-sweeps
-      const int pc = n >= 256 ? AFH_PROF_GSRB : -1;
+      // timed on levels of >= 256 boxes without electrode boxes, as the split
+      // half-sweeps
+      const int pc = n >= 256 && !var ? AFH_PROF_GSRB : -1;
       prof_mark(t, pc);
-      const double *rh = t->ccv(mg->d.i_rhs);
-      const int32_t *ids = t->ids.at(lvl);
-      // several boxes per wave: four 4^2, two 8^2
-      if (t->cyl() && t->nc == 4)
-        hipLaunchKernelGGL((k2_pair_box_cyl<4, 16>), dim3((n + 3) / 4), dim3(64), 0, t->stream,
-                           src, dst, rh, phi, t->d_boxes, ids, n, t->bsz, cf, g);
-      else if (t->cyl() && t->nc == 8)
-        hipLaunchKernelGGL((k2_pair_box_cyl<8, 32>), dim3((n + 1) / 2), dim3(64), 0, t->stream,
-                           src, dst, rh, phi, t->d_boxes, ids, n, t->bsz, cf, g);
-      else if (t->cyl())
-        hipLaunchKernelGGL(k2_pair_box_cyl<16>, dim3(n), dim3(64), 0, t->stream, src, dst, rh,
-                           phi, t->d_boxes, ids, n, t->bsz, cf, g);
-      else if (t->nc == 4)
-        hipLaunchKernelGGL((k2_pair_box<4, 16>), dim3((n + 3) / 4), dim3(64), 0, t->stream, src,
-                           dst, rh, phi, t->d_boxes, ids, n, t->bsz, cf, g);
-      else if (t->nc == 8)
-        hipLaunchKernelGGL((k2_pair_box<8, 32>), dim3((n + 1) / 2), dim3(64), 0, t->stream, src,
-                           dst, rh, phi, t->d_boxes, ids, n, t->bsz, cf, g);
-      else
-        hipLaunchKernelGGL(k2_pair_box<16>, dim3(n), dim3(64), 0, t->stream, src, dst, rh, phi,
-                           t->d_boxes, ids, n, t->bsz, cf, g);
+      pair_launch(mg, lvl, var, (p & 1) ? mg->alt : phi, (p & 1) ? phi : mg->alt, 2 * p);
       H2_LAUNCH("k2_pair_box");
       // a red+black pair reads phi and rhs and writes phi once = 24 B/cell
       prof_end(t, pc, 24.0 * t->nc * t->nc * n);
+    }
+    if (var) {
+      const int nv = mg->ids_v.n(lvl);
+      hipLaunchKernelGGL(k2_rhs_roundtrip, grid2(t->nc * t->nc, nv), blk2(t->nc * t->nc), 0,
+                         t->stream, t->ccv(mg->d.i_rhs), mg->ids_v.at(lvl), t->nc, t->bsz,
+                         mg->d_bp, 2 * nc_);
+      H2_LAUNCH("k2_rhs_roundtrip");
     }
     if (up && !skip_corners) {
       hipLaunchKernelGGL(k2_corners, dim3((4 * n + NT - 1) / NT), dim3(NT), 0, t->stream,
@@ -3166,106 +2879,78 @@ static int32_t gsrb_boxes(afh_mg *mg, int lvl, bool up, bool skip_corners = fals
     }
     return AFH_OK;
   }
-  if (var) {
-    // the constant kernel on the level's ordinary boxes, k2_gsrb_v on the rest
-    const int ncst = mg->ids_c.n(lvl), nv = mg->ids_v.n(lvl);
-    for (int s = 1; s <= 2 * nc_; s++) {
-      if (ncst) {
-        hipLaunchKernelGGL(k2_gsrb, grid2(t->nc * t->nc / 2, ncst), blk2(t->nc * t->nc / 2), 0,
-                           t->stream, t->ccv(mg->d.i_phi), t->ccv(mg->d.i_rhs),
-                           mg->ids_c.at(lvl), t->nc, t->bsz, mg->lvl_c[lvl - 1], s);
-        H2_LAUNCH("k2_gsrb");
-      }
-      hipLaunchKernelGGL(k2_gsrb_v, grid2(t->nc * t->nc, nv), blk2(t->nc * t->nc), 0, t->stream,
+  // the split half-sweeps: k2_gsrb on the level's ordinary boxes, k2_gsrb_v on
+  // its electrode boxes
+  const LevelList &L = var ? mg->ids_c : t->ids;
+  const int ncst = L.n(lvl), nv = var ? mg->ids_v.n(lvl) : 0, w = t->nc * t->nc / 2;
+  for (int s = 1; s <= 2 * nc_; s++) {
+    if (ncst) {
+      // timed on levels of >= 256 boxes without electrode boxes, as
+      // libafivo_hip's pair: the small levels' launches are launch-bound,
+      // another regime
+      const int pc = n >= 256 && !var ? AFH_PROF_GSRB : -1;
+      prof_mark(t, pc);
+      if (t->cyl())
+        hipLaunchKernelGGL(k2_gsrb<StCyl>, grid2(w, ncst), blk2(w), cyl_lds(t), t->stream,
+                           t->ccv(mg->d.i_phi), t->ccv(mg->d.i_rhs), L.at(lvl), t->nc, t->bsz,
+                           StCyl{mg->lvl_c[lvl - 1]}, s, t->d_boxes);
+      else
+        hipLaunchKernelGGL(k2_gsrb<StConst>, grid2(w, ncst), blk2(w), 0, t->stream,
+                           t->ccv(mg->d.i_phi), t->ccv(mg->d.i_rhs), L.at(lvl), t->nc, t->bsz,
+                           StConst{mg->lvl_c[lvl - 1]}, s, StConst::Meta{});
+      H2_LAUNCH("k2_gsrb");
+      prof_end(t, pc, 16.0 * t->nc * t->nc * n);
+    }
+    if (var) {
+      hipLaunchKernelGGL(k2_gsrb_v, grid2(2 * w, nv), blk2(2 * w), 0, t->stream,
                          t->ccv(mg->d.i_phi), t->ccv(mg->d.i_rhs), mg->ids_v.at(lvl), t->nc,
                          t->bsz, mg->d_vp, mg->d_bp, s);
       H2_LAUNCH("k2_gsrb_v");
-      if (int32_t e = gc_lvl(t, lvl, mg->d.i_phi, up && s == 2 * nc_)) return e;
-    }
-    return AFH_OK;
-  }
-  for (int s = 1; s <= 2 * nc_; s++) {
-    if (n) {
-      // timed on levels of >= 256 boxes, as libafivo_hip's pair: the small
-      // levels' launches are launch-bound, another regime
-      const int pc = n >= 256 ? AFH_PROF_GSRB : -1;
-      prof_mark(t, pc);
-      if (t->cyl())
-        hipLaunchKernelGGL(k2_gsrb_cyl, grid2(t->nc * t->nc / 2, n), blk2(t->nc * t->nc / 2),
-                           cyl_lds(t), t->stream, t->ccv(mg->d.i_phi), t->ccv(mg->d.i_rhs),
-                           t->d_boxes, t->ids.at(lvl), t->nc, t->bsz, mg->lvl_c[lvl - 1], s);
-      else
-      hipLaunchKernelGGL(k2_gsrb, grid2(t->nc * t->nc / 2, n), blk2(t->nc * t->nc / 2), 0, t->stream,
-                         t->ccv(mg->d.i_phi), t->ccv(mg->d.i_rhs), t->ids.at(lvl), t->nc,
-                         t->bsz, mg->lvl_c[lvl - 1], s);
-      H2_LAUNCH("k2_gsrb");
-      prof_end(t, pc, 16.0 * t->nc * t->nc * n);
     }
     if (int32_t e = gc_lvl(t, lvl, mg->d.i_phi, up && s == 2 * nc_)) return e;
   }
   return AFH_OK;
 }
 
-// k2_parent_rhs over the parents of level lvl (a Cartesian tree): the
-// constant kernel on the ordinary boxes, k2_parent_rhs_v on electrode boxes
+// k2_parent_rhs over the parents of level lvl: the level's stencil on the
+// ordinary boxes, StVar on electrode boxes
 static int32_t parent_rhs(afh_mg *mg, int lvl, int copy) {
   afh_tree *t = mg->t;
   const LevelList &L = cst(mg, t->parents, mg->parents_c);
-  const int ncst = L.n(lvl), nv = mg->any_var ? mg->parents_v.n(lvl) : 0;
-  if (ncst) {
-    hipLaunchKernelGGL(k2_parent_rhs, grid2(t->bsz, ncst), blk2(t->bsz), 0, t->stream,
-                       t->ccv(mg->d.i_phi), t->ccv(mg->d.i_rhs), t->ccv(mg->d.i_tmp),
-                       L.at(lvl), t->nc, t->bsz, mg->lvl_c[lvl - 1], copy);
-    H2_LAUNCH("k2_parent_rhs");
-  }
-  if (nv) {
-    hipLaunchKernelGGL(k2_parent_rhs_v, grid2(t->bsz, nv), blk2(t->bsz), 0, t->stream,
-                       t->ccv(mg->d.i_phi), t->ccv(mg->d.i_rhs), t->ccv(mg->d.i_tmp),
-                       mg->parents_v.at(lvl), t->nc, t->bsz, mg->d_vp, mg->d_bp, copy);
-    H2_LAUNCH("k2_parent_rhs_v");
-  }
+  auto launch = [&](const LevelList &B, bool var) {
+    const int n = B.n(lvl);
+    if (!n) return;
+    with_stencil(mg, lvl, var, [&](auto st, size_t lds) {
+      hipLaunchKernelGGL(k2_parent_rhs<decltype(st)>, grid2(t->bsz, n), blk2(t->bsz), lds,
+                         t->stream, t->ccv(mg->d.i_phi), t->ccv(mg->d.i_rhs),
+                         t->ccv(mg->d.i_tmp), B.at(lvl), t->nc, t->bsz, st, copy,
+                         stencil_meta<decltype(st)>(t));
+    });
+  };
+  launch(L, false);
+  if (mg->any_var) launch(mg->parents_v, true);
+  H2_LAUNCH("k2_parent_rhs");
   return AFH_OK;
 }
 
 // update_coarse (691-738)
 static int32_t update_coarse(afh_mg *mg, int lvl) {
   afh_tree *t = mg->t;
-  const int n = t->ids.n(lvl);
-  if (n && t->cyl()) {
-    hipLaunchKernelGGL(k2_rstr_fas_cyl, grid2(t->nc * t->nc / 4, n), blk2(t->nc * t->nc / 4),
-                       cyl_lds(t), t->stream, t->ccv(mg->d.i_phi), t->ccv(mg->d.i_rhs),
-                       t->ccv(mg->d.i_tmp), t->d_boxes, t->ids.at(lvl), t->nc, t->bsz,
-                       mg->lvl_c[lvl - 1]);
-    H2_LAUNCH("k2_rstr_fas_cyl");
-  } else if (n) {
-    const LevelList &L = cst(mg, t->ids, mg->ids_c);
-    const int ncst = L.n(lvl), nv = mg->any_var ? mg->ids_v.n(lvl) : 0;
-    if (ncst) {
-      hipLaunchKernelGGL(k2_rstr_fas, grid2(t->nc * t->nc / 4, ncst),
-                         blk2(t->nc * t->nc / 4), 0, t->stream, t->ccv(mg->d.i_phi),
-                         t->ccv(mg->d.i_rhs), t->ccv(mg->d.i_tmp), t->d_boxes, L.at(lvl), t->nc,
-                         t->bsz, mg->lvl_c[lvl - 1]);
-      H2_LAUNCH("k2_rstr_fas");
-    }
-    if (nv) {
-      hipLaunchKernelGGL(k2_rstr_fas_v, grid2(t->nc * t->nc / 4, nv), blk2(t->nc * t->nc / 4),
-                         0, t->stream, t->ccv(mg->d.i_phi), t->ccv(mg->d.i_rhs),
-                         t->ccv(mg->d.i_tmp), t->d_boxes, mg->ids_v.at(lvl), t->nc, t->bsz,
-                         mg->d_vp, mg->d_bp);
-      H2_LAUNCH("k2_rstr_fas_v");
-    }
-  }
+  const LevelList &L = cst(mg, t->ids, mg->ids_c);
+  auto launch = [&](const LevelList &B, bool var) {
+    const int n = B.n(lvl), w = t->nc * t->nc / 4;
+    if (!n) return;
+    with_stencil(mg, lvl, var, [&](auto st, size_t lds) {
+      hipLaunchKernelGGL(k2_rstr_fas<decltype(st)>, grid2(w, n), blk2(w), lds, t->stream,
+                         t->ccv(mg->d.i_phi), t->ccv(mg->d.i_rhs), t->ccv(mg->d.i_tmp),
+                         t->d_boxes, B.at(lvl), t->nc, t->bsz, st);
+    });
+  };
+  launch(L, false);
+  if (mg->any_var) launch(mg->ids_v, true);
+  H2_LAUNCH("k2_rstr_fas");
   if (int32_t e = gc_lvl(t, lvl - 1, mg->d.i_phi, true)) return e;
-  const int np = t->parents.n(lvl - 1);
-  if (np && t->cyl()) {
-    hipLaunchKernelGGL(k2_parent_rhs_cyl, grid2(t->bsz, np), blk2(t->bsz), cyl_lds(t), t->stream,
-                       t->ccv(mg->d.i_phi), t->ccv(mg->d.i_rhs), t->ccv(mg->d.i_tmp), t->d_boxes,
-                       t->parents.at(lvl - 1), t->nc, t->bsz, mg->lvl_c[lvl - 2], 1);
-    H2_LAUNCH("k2_parent_rhs_cyl");
-  } else if (np) {
-    if (int32_t e = parent_rhs(mg, lvl - 1, 1)) return e;
-  }
-  return AFH_OK;
+  return parent_rhs(mg, lvl - 1, 1);
 }
 
 // correct_children of the parents of level lvl-1 (624-646)
@@ -3301,63 +2986,43 @@ static const LevelList &split_of(const afh_mg *mg, const LevelList &L, const Lev
   return *v = &mg->ids_v, mg->ids_c;
 }
 
-// k2_residual_v on boxes [l0, l1] of the variable list V
-static int32_t residual_var(afh_mg *mg, const LevelList &V, int l0, int l1, bool fold) {
+// k2_residual on the boxes of levels l0 .. l1 of list B (var: a list of
+// electrode boxes); l1 > l0: each box's coefficients by its level
+static int32_t residual_launch(afh_mg *mg, const LevelList &B, bool var, int l0, int l1,
+                               bool fold) {
   afh_tree *t = mg->t;
-  const int n = V.off[l1] - V.off[l0 - 1];
+  const int n = B.off[l1] - B.off[l0 - 1], w = t->nc * t->nc;
   if (!n) return AFH_OK;
-  hipLaunchKernelGGL(k2_residual_v, grid2(t->nc * t->nc, n), blk2(t->nc * t->nc), 0, t->stream,
-                     t->ccv(mg->d.i_phi), t->ccv(mg->d.i_rhs), t->ccv(mg->d.i_tmp), V.at(l0),
-                     t->nc, t->bsz, mg->d_vp, mg->d_bp,
-                     fold ? t->red + 3 * RED_SHARDS : nullptr);
-  H2_LAUNCH("k2_residual_v");
-  return AFH_OK;
-}
-
-static int32_t residual_lvl(afh_mg *mg, int lvl, const LevelList &L_, bool fold) {
-  afh_tree *t = mg->t;
-  const LevelList *V;
-  const LevelList &L = split_of(mg, L_, &V);
-  if (V)
-    if (int32_t e = residual_var(mg, *V, lvl, lvl, fold)) return e;
-  const int n = L.n(lvl);
-  if (!n) return AFH_OK;
-  if (t->cyl())
-    hipLaunchKernelGGL(k2_residual_cyl, grid2(t->nc * t->nc, n), blk2(t->nc * t->nc), cyl_lds(t),
-                       t->stream, t->ccv(mg->d.i_phi), t->ccv(mg->d.i_rhs), t->ccv(mg->d.i_tmp),
-                       L.at(lvl), t->nc, t->bsz, mg->lvl_c[lvl - 1],
-                       fold ? t->red + 3 * RED_SHARDS : nullptr, nullptr, t->d_boxes);
-  else
-  hipLaunchKernelGGL(k2_residual, grid2(t->nc * t->nc, n), blk2(t->nc * t->nc), 0, t->stream,
-                     t->ccv(mg->d.i_phi), t->ccv(mg->d.i_rhs), t->ccv(mg->d.i_tmp), L.at(lvl),
-                     t->nc, t->bsz, mg->lvl_c[lvl - 1],
-                     fold ? t->red + 3 * RED_SHARDS : nullptr, nullptr, nullptr);
+  const bool all = l1 > l0 && !var;
+  with_stencil(mg, l0, var, [&](auto st, size_t lds) {
+    hipLaunchKernelGGL(k2_residual<decltype(st)>, grid2(w, n), blk2(w), lds, t->stream,
+                       t->ccv(mg->d.i_phi), t->ccv(mg->d.i_rhs), t->ccv(mg->d.i_tmp), B.at(l0),
+                       t->nc, t->bsz, st, fold ? t->red + 3 * RED_SHARDS : nullptr,
+                       all ? mg->d_lvl_c : nullptr, t->d_boxes);
+  });
   H2_LAUNCH("k2_residual");
   return AFH_OK;
 }
 
+static int32_t residual_lvl(afh_mg *mg, int lvl, const LevelList &L_, bool fold) {
+  const LevelList *V;
+  const LevelList &L = split_of(mg, L_, &V);
+  if (V)
+    if (int32_t e = residual_launch(mg, *V, true, lvl, lvl, fold)) return e;
+  return residual_launch(mg, L, false, lvl, lvl, fold);
+}
+
 // the residual of levels 1 .. max_lvl of list L in one launch (each box's
 // coefficients by its level; false: max_lvl boxes exceed the grid's y limit)
-// (err: a launch error of the variable boxes' part; the list then counts as
-// done and the caller returns the error)
+// (err: a launch error; the list then counts as done and the caller returns
+// the error)
 static bool residual_all(afh_mg *mg, int max_lvl, const LevelList &L_, bool fold,
                          int32_t &err) {
-  afh_tree *t = mg->t;
   if (!mg->all_lvl || L_.off[max_lvl] - L_.off[0] > 65535) return false;
   const LevelList *V;
   const LevelList &L = split_of(mg, L_, &V);
-  if (V && (err = residual_var(mg, *V, 1, max_lvl, fold))) return true;
-  const int n = L.off[max_lvl] - L.off[0];
-  if (n && t->cyl())
-    hipLaunchKernelGGL(k2_residual_cyl, grid2(t->nc * t->nc, n), blk2(t->nc * t->nc), cyl_lds(t),
-                       t->stream, t->ccv(mg->d.i_phi), t->ccv(mg->d.i_rhs), t->ccv(mg->d.i_tmp),
-                       L.at(1), t->nc, t->bsz, mg->lvl_c[0],
-                       fold ? t->red + 3 * RED_SHARDS : nullptr, mg->d_lvl_c, t->d_boxes);
-  else if (n)
-    hipLaunchKernelGGL(k2_residual, grid2(t->nc * t->nc, n), blk2(t->nc * t->nc), 0, t->stream,
-                       t->ccv(mg->d.i_phi), t->ccv(mg->d.i_rhs), t->ccv(mg->d.i_tmp), L.at(1),
-                       t->nc, t->bsz, mg->lvl_c[0], fold ? t->red + 3 * RED_SHARDS : nullptr,
-                       mg->d_lvl_c, t->d_boxes);
+  if (V && (err = residual_launch(mg, *V, true, 1, max_lvl, fold))) return true;
+  err = residual_launch(mg, L, false, 1, max_lvl, fold);
   return true;
 }
 
@@ -3465,7 +3130,6 @@ int32_t afh_mg_fas_fmg(afh_mg *mg, int32_t set_residual, int32_t have_guess) {
   if (!mg) return set_error(AFH_ERR_ARG, "null mg");
   afh_tree *t = mg->t;
   double *phi = t->ccv(mg->d.i_phi), *rhs = t->ccv(mg->d.i_rhs), *tmp = t->ccv(mg->d.i_tmp);
-  const int nc = t->nc;
   int32_t e;
   if ((e = prepare_var(mg))) return e;
   if (have_guess) {
@@ -3481,15 +3145,7 @@ int32_t afh_mg_fas_fmg(afh_mg *mg, int32_t set_residual, int32_t have_guess) {
         H2_LAUNCH("k2_restrict");
       }
       if ((e = gc_lvl(t, l - 1, mg->d.i_phi, true))) return e;
-      const int np = t->parents.n(l - 1);
-      if (np && t->cyl()) {
-        hipLaunchKernelGGL(k2_parent_rhs_cyl, grid2(t->bsz, np), blk2(t->bsz), cyl_lds(t),
-                           t->stream, phi, rhs, tmp, t->d_boxes, t->parents.at(l - 1), nc, t->bsz,
-                           mg->lvl_c[l - 2], 0);
-        H2_LAUNCH("k2_parent_rhs_cyl");
-      } else if (np) {
-        if ((e = parent_rhs(mg, l - 1, 0))) return e;
-      }
+      if ((e = parent_rhs(mg, l - 1, 0))) return e;
     }
   } else {
     // init_phi_rhs (779-799)
@@ -3961,96 +3617,36 @@ static int32_t update(afh_fluid *f, double dt, int32_t s_deriv, int32_t n_prev,
     const dim3 bk = blk2(t->nc * t->nc);
     const int32_t *ids = t->leaves.at(l);
     unsigned long long *red = t->red + 2 * RED_SHARDS;
-    if (f->d.n_ions > 0) {
-      // the sibling kernels with the ions' flux divergences
-      const bool photo = f->d.i_photo > 0, cyl = t->cyl(), mask = M.lsf != nullptr;
-      const PhotoArgs P{photo ? t->ccv(f->d.i_photo) : nullptr, f->d.photo_species - 1};
-      IonUpdArgs I;
-      I.n = f->d.n_ions;
-      for (int q = 0; q < AFH_MAX_IONS; q++) {
-        I.s[q] = q < I.n ? f->d.ion_species[q] - 1 : 0;
-        I.F[q] = q < I.n ? t->fcv(f->d.f_ion_flux[q]) : nullptr;
-      }
-      switch (A.ns) {
-#define AFH2_UPDK(N, C, PH, MK)                                                              \
-  hipLaunchKernelGGL((k2_update_ions<N, C, PH, MK>), g, bk, 0, t->stream, A, ids, t->d_boxes, \
-                     t->nc, t->bsz, t->fsz, red, P, M, I)
-#define AFH2_UPD(N)                                    \
-  case N:                                              \
-    if (mask && photo) AFH2_UPDK(N, false, true, true); \
-    else if (mask) AFH2_UPDK(N, false, false, true);    \
-    else if (cyl && photo) AFH2_UPDK(N, true, true, false); \
-    else if (cyl) AFH2_UPDK(N, true, false, false);     \
-    else if (photo) AFH2_UPDK(N, false, true, false);   \
-    else AFH2_UPDK(N, false, false, false);             \
-    break;
-        AFH2_UPD(1) AFH2_UPD(2) AFH2_UPD(3) AFH2_UPD(4) AFH2_UPD(5) AFH2_UPD(6) AFH2_UPD(7)
-        AFH2_UPD(8) AFH2_UPD(9) AFH2_UPD(10) AFH2_UPD(11) AFH2_UPD(12)
-      default: AFH2_UPD(MAXS)
-#undef AFH2_UPD
-#undef AFH2_UPDK
-      }
-    } else if (M.lsf) {
-      // the sibling kernels with set_box_mask (and the photoionization term)
-      const PhotoArgs P{f->d.i_photo > 0 ? t->ccv(f->d.i_photo) : nullptr,
-                        f->d.photo_species - 1};
-      const bool photo = f->d.i_photo > 0;
-      switch (A.ns) {
-#define AFH2_UPD(N)                                                                         \
-  case N:                                                                                   \
-    if (photo)                                                                              \
-      hipLaunchKernelGGL(k2_update_photo_mask<N>, g, bk, 0, t->stream, A, ids, t->d_boxes,  \
-                         t->nc, t->bsz, t->fsz, red, P, M);                                 \
-    else                                                                                    \
-      hipLaunchKernelGGL(k2_update_mask<N>, g, bk, 0, t->stream, A, ids, t->d_boxes, t->nc, \
-                         t->bsz, t->fsz, red, M);                                           \
-    break;
-        AFH2_UPD(1) AFH2_UPD(2) AFH2_UPD(3) AFH2_UPD(4) AFH2_UPD(5) AFH2_UPD(6) AFH2_UPD(7)
-        AFH2_UPD(8) AFH2_UPD(9) AFH2_UPD(10) AFH2_UPD(11) AFH2_UPD(12)
-      default: AFH2_UPD(MAXS)
-#undef AFH2_UPD
-      }
-    } else if (f->d.i_photo > 0) {
-      // the sibling kernels with the photoionization term
-      const PhotoArgs P{t->ccv(f->d.i_photo), f->d.photo_species - 1};
-      const bool cyl = t->cyl();
-      switch (A.ns) {
-#define AFH2_UPD(N)                                                                         \
-  case N:                                                                                   \
-    if (cyl)                                                                                \
-      hipLaunchKernelGGL(k2_update_cyl_photo<N>, g, bk, 0, t->stream, A, ids, t->d_boxes,   \
-                         t->nc, t->bsz, t->fsz, red, P);                                    \
-    else                                                                                    \
-      hipLaunchKernelGGL(k2_update_photo<N>, g, bk, 0, t->stream, A, ids, t->d_boxes,       \
-                         t->nc, t->bsz, t->fsz, red, P);                                    \
-    break;
-        AFH2_UPD(1) AFH2_UPD(2) AFH2_UPD(3) AFH2_UPD(4) AFH2_UPD(5) AFH2_UPD(6) AFH2_UPD(7)
-        AFH2_UPD(8) AFH2_UPD(9) AFH2_UPD(10) AFH2_UPD(11) AFH2_UPD(12)
-      default: AFH2_UPD(MAXS)
-#undef AFH2_UPD
-      }
-    } else if (t->cyl()) {
-      switch (A.ns) {
-#define AFH2_UPD(N) \
-  case N: hipLaunchKernelGGL(k2_update_cyl<N>, g, bk, 0, t->stream, A, ids, t->d_boxes, t->nc, t->bsz, t->fsz, red); break;
-        AFH2_UPD(1) AFH2_UPD(2) AFH2_UPD(3) AFH2_UPD(4) AFH2_UPD(5) AFH2_UPD(6) AFH2_UPD(7)
-        AFH2_UPD(8) AFH2_UPD(9) AFH2_UPD(10) AFH2_UPD(11) AFH2_UPD(12)
-#undef AFH2_UPD
-      default:
-        hipLaunchKernelGGL(k2_update_cyl<MAXS>, g, bk, 0, t->stream, A, ids, t->d_boxes, t->nc,
-                           t->bsz, t->fsz, red);
-      }
-    } else
-    switch (A.ns) {
-#define AFH2_UPD(N) \
-  case N: hipLaunchKernelGGL(k2_update<N>, g, bk, 0, t->stream, A, ids, t->d_boxes, t->nc, t->bsz, t->fsz, red); break;
-      AFH2_UPD(1) AFH2_UPD(2) AFH2_UPD(3) AFH2_UPD(4) AFH2_UPD(5) AFH2_UPD(6) AFH2_UPD(7)
-      AFH2_UPD(8) AFH2_UPD(9) AFH2_UPD(10) AFH2_UPD(11) AFH2_UPD(12)
-#undef AFH2_UPD
-    default:
-      hipLaunchKernelGGL(k2_update<MAXS>, g, bk, 0, t->stream, A, ids, t->d_boxes,
-                         t->nc, t->bsz, t->fsz, red);
+    // the argument blocks of the features (the launch takes those that are on)
+    const bool photo = f->d.i_photo > 0, mask = M.lsf != nullptr, ions = f->d.n_ions > 0;
+    const PhotoArgs P{photo ? t->ccv(f->d.i_photo) : nullptr, f->d.photo_species - 1};
+    IonUpdArgs I;
+    I.n = f->d.n_ions;
+    for (int q = 0; q < AFH_MAX_IONS; q++) {
+      I.s[q] = q < I.n ? f->d.ion_species[q] - 1 : 0;
+      I.F[q] = q < I.n ? t->fcv(f->d.f_ion_flux[q]) : nullptr;
     }
+    // one instantiation per combination of Cartesian / cylindrical / masked
+    // (the mask excludes cyl, above), photo and ions
+    with_species_count(A.ns, [&](auto ns) {
+      auto kind = [&](auto cyl_, auto mask_) {
+        with_flag(photo, [&](auto photo_) {
+          with_flag(ions, [&](auto ions_) {
+            constexpr bool C = decltype(cyl_)::value, PH = decltype(photo_)::value,
+                           MK = decltype(mask_)::value, IO = decltype(ions_)::value;
+            UpdOpt<PH, MK, IO> O;
+            if constexpr (PH) static_cast<PhotoArgs &>(O) = P;
+            if constexpr (MK) static_cast<MaskArgs &>(O) = M;
+            if constexpr (IO) static_cast<IonUpdArgs &>(O) = I;
+            hipLaunchKernelGGL((k2_update<decltype(ns)::value, C, PH, MK, IO>), g, bk, 0,
+                               t->stream, A, ids, t->d_boxes, t->nc, t->bsz, t->fsz, O, red);
+          });
+        });
+      };
+      if (mask) kind(std::false_type{}, std::true_type{});
+      else if (t->cyl()) kind(std::true_type{}, std::false_type{});
+      else kind(std::false_type{}, std::false_type{});
+    });
     H2_LAUNCH("k2_update");
   }
   dt_lim[0] = 1e100, dt_lim[1] = 1e100;

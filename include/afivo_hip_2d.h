@@ -186,7 +186,7 @@ int32_t afh_photoi_helmh_compute(afh_mg *const *modes, int32_t n_modes,
  * a level-1 stencil changes). Setting or removing a stencil or a distance
  * list drops the multigrid's captured hipGraphs: the next V-cycle runs
  * eagerly and captures again. Levels with variable boxes smooth with the
- * fused pair's variable form (k2_pair_box_v; AFH_PAIR2D=0: split
+ * fused pair's variable form (k2_pair_box<VAR = true>; AFH_PAIR2D=0: split
  * half-sweeps, k2_gsrb + k2_gsrb_v), bitwise the same;
  * levels and trees without them launch what they launched before.
  * afh_mg_compute_phi_gradient corrects the faces of the leaf boxes with a

@@ -6,7 +6,7 @@ switched on in memory; the same host tree for both -- the deck's coarse grid
 refined uniformly until the two finest levels hold 256 and 1024 boxes of 8^2
 cells, the levels afh_profile_enable(AFH_PROF_GSRB) times -- and the same
 right-hand side. V-cycles run eagerly while kernels are timed, so the figure
-is the kernel's (k2_pair_box / k2_pair_box_cyl), alternating the two trees.
+is the kernel's (k2_pair_box / k2_pair_box<CYL = true>), alternating the two trees.
 
     python3 scripts/cyl_step_time.py [--cycles N] [--rounds R] [--json PATH]
 

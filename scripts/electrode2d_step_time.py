@@ -8,7 +8,7 @@ is timed: copy_current_state, the two Heun stages (advance), field_compute
 with its V-cycles through the electrode stencils, and the state put back, so
 that every repetition does the same work. Medians over --rounds rounds of
 --reps repetitions each, wall clock from a drained stream to a drained stream,
-once with AFH_PAIR2D=1 (k2_pair_box_v on the levels with variable boxes) and
+once with AFH_PAIR2D=1 (k2_pair_box<VAR = true> on the levels with variable boxes) and
 once with AFH_PAIR2D=0 (k2_gsrb + k2_gsrb_v + k2_gc), plus the time of one
 V-cycle alone.
 

@@ -24,7 +24,7 @@ def apply_v(phi, v):
 
 def residual_v(phi, rhs, v, b):
     """residual_box: rhs - (L phi - bc_correction) over the interior
-    (k2_residual_v)."""
+    (k2_residual<StVar>)."""
     a = apply_v(phi, v)
     if b is not None:
         a = a - b
@@ -107,7 +107,7 @@ def fill_sides(boxes, neighbors, bc):
 
 
 def rstr_fas_v(phi, rhs, v, b):
-    """update_coarse for a child with a variable stencil (k2_rstr_fas_v): the
+    """update_coarse for a child with a variable stencil (k2_rstr_fas<StVar>): the
     restricted residual and phi, (nc/2)^2 each: 0.25 * sum(cc(i_f:i_f+1,
     j_f:j_f+1)) in column-major section order."""
     res = residual_v(phi, rhs, v, b)
@@ -120,7 +120,7 @@ def rstr_fas_v(phi, rhs, v, b):
 
 def parent_rhs_v(phi, rhs, tmp, v, b):
     """rhs = L phi + tmp (L phi - bc_correction on the interior, the old rhs
-    on the ghost cells), tmp = phi over the whole block (k2_parent_rhs_v)."""
+    on the ghost cells), tmp = phi over the whole block (k2_parent_rhs<StVar>)."""
     r = rhs.copy()
     a = apply_v(phi, v)
     if b is not None:

@@ -169,7 +169,7 @@ def _vcycle_fields(cyl, pair, monkeypatch, n=1, seed=5):
 
 
 def test_fused_pair_equals_split_sweeps(monkeypatch):
-    """k2_pair_box_cyl against k2_gsrb_cyl + the level fills, through whole
+    """k2_pair_box<CYL = true> against k2_gsrb<StCyl> + the level fills, through whole
     V-cycles on the AMR tree (same-level neighbours across r- and z-faces,
     physical and refinement boundaries): bitwise."""
     _, af, _, _, _ = _state()
@@ -238,8 +238,8 @@ def test_down_leg_coarse_rhs(monkeypatch):
 
 @pytest.mark.parametrize("nc", [6, 12])
 def test_down_leg_coarse_rhs_box_size(nc, monkeypatch):
-    """The same at box sizes without kernels of their own (k2_gsrb_cyl,
-    k2_residual_cyl, k2_restrict_cyl and k2_parent_rhs_cyl decode by division;
+    """The same at box sizes without kernels of their own (k2_gsrb<StCyl>,
+    k2_residual<StCyl>, k2_restrict<StCyl> and k2_parent_rhs<StCyl> decode by division;
     the coefficient table of 4 nc doubles)."""
     _down_leg_coarse_rhs(monkeypatch, nc)
 

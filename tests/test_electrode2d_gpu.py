@@ -243,7 +243,7 @@ def test_driver_rejects_cylindrical_electrode():
 def test_residual_and_rhs_roundtrip_bitwise(which, monkeypatch):
     """After a V-cycle with set_residual, tmp of every variable box is rhs -
     (L phi - bc_correction) of the phi and rhs the device holds
-    (k2_residual_v), and the rhs of a variable leaf of the finest level -- 8
+    (k2_residual<StVar>), and the rhs of a variable leaf of the finest level -- 8
     half-sweeps, nothing else writes it -- is 8 round trips (rhs + b) - b of
     what was put (k2_gsrb_v / k2_rhs_roundtrip)."""
     for pair in (True, False):
@@ -275,9 +275,9 @@ def test_down_leg_bitwise(monkeypatch):
     """One V-cycle's down leg on tree A with the split sweeps, against numpy
     box by box: the ghost fill, four half sweeps with fills (k2_gsrb_v on the
     two variable level-2 boxes, k2_gsrb on the other two), the children's
-    residual and phi restricted into the level-1 box (k2_rstr_fas_v,
+    residual and phi restricted into the level-1 box (k2_rstr_fas<StVar>,
     k2_rstr_fas), its ghost fill, and rhs = L phi - bc_correction + tmp with
-    the level-1 box's own variable stencil (k2_parent_rhs_v). fas_vcycle
+    the level-1 box's own variable stencil (k2_parent_rhs<StVar>). fas_vcycle
     without the residual pass leaves that rhs on level 1; it holds phi of the
     level-2 boxes after the sweeps through the restricted phi. The level-2
     rhs is the 8 round trips of the whole cycle."""
@@ -345,7 +345,7 @@ def _down_leg(monkeypatch, nc):
 
 def test_vcycles_converge_through_the_electrode(monkeypatch):
     """FAS V-cycles on tree B with variable boxes on every level (k2_gsrb_v,
-    k2_rstr_fas_v, k2_parent_rhs_v and the level-1 rows together): the
+    k2_rstr_fas<StVar>, k2_parent_rhs<StVar> and the level-1 rows together): the
     residual falls to rounding."""
     sim = _sim("B", monkeypatch)
     _start(sim)
@@ -358,7 +358,7 @@ def test_vcycles_converge_through_the_electrode(monkeypatch):
 @pytest.mark.parametrize("which,nc", [("A", 8), ("B", 8), ("A", 4), ("A", 16), ("A", 6),
                                       ("A", 12)])
 def test_fused_variable_pair_equals_split(which, nc, monkeypatch):
-    """AFH_PAIR2D=1 (k2_pair_box_v on the levels with variable boxes) against
+    """AFH_PAIR2D=1 (k2_pair_box<VAR = true> on the levels with variable boxes) against
     AFH_PAIR2D=0 (k2_gsrb + k2_gsrb_v + k2_gc twice), bitwise: after a
     V-cycle without the residual pass -- the rhs and tmp of the coarser levels
     are then as the down leg left them (restriction and rhs = L phi + tmp),
@@ -615,8 +615,8 @@ def test_electrode_species_bc_bitwise(neumann_zero, monkeypatch):
 
 @pytest.mark.parametrize("case", [CASE, CASE + "_photoi"])
 def test_update_mask_bitwise(case, monkeypatch):
-    """k2_update_mask / k2_update_photo_mask against the unmasked update of
-    the same state: a cell with lsf <= 0 is the weighted sum of the previous
+    """k2_update<MASK = true>, with and without PHOTO, against the unmasked
+    update of the same state: a cell with lsf <= 0 is the weighted sum of the previous
     states, every other cell the unmasked result; the last step's chemistry
     limit is the minimum over the leaves that have a cell to update, and
     1e100 when the only leaves given such cells lie inside the electrode."""

@@ -432,11 +432,12 @@ def test_forward_euler_and_fold_bitwise(cyl):
     sim.tree.close()
 
 
-def test_update_with_photoionization():
-    """Cylindrical, the photoionization deck with its photo_species mobile:
-    the rate is added to the electrons and that ion before their divergences
-    (y + dt * photo, then the flux terms)."""
-    sim = _sim(True, 3, case=PHOTO_CASE, reactions=False)
+def _photo_update(cyl, masked):
+    """The photoionization deck with its photo_species mobile: the rate is
+    added to the electrons and that ion before their divergences (y + dt *
+    photo, then the flux terms); masked: a cell whose level set is <= 0 keeps
+    the previous state, without the rate."""
+    sim = _sim(cyl, 3, case=PHOTO_CASE, reactions=False)
     assert sim.photoi and sim.photo_species in [sp for sp, _, _ in sim.ions]
     af = sim.af
     dt = 1e-12
@@ -444,19 +445,42 @@ def test_update_with_photoionization():
     _random_state(sim, 32, s=2)
     photo = 1e26 * np.random.default_rng(33).random(_shape(af))
     sim.tree.put_cc(sim.i_photo, photo)
+    mask = None
+    if masked:
+        lsf = np.random.default_rng(34).standard_normal(_shape(af))
+        lsf[af.leaves()[0] - 1] = -1.0  # a leaf with no cell to update
+        sim.tree.put_cc(sim.i_tmp, lsf)
+        sim.fluid.set_update_mask(sim.i_tmp)
+        mask = lsf <= 0
     e_slot = _flux_vars(sim)[0][3]
     add = {e_slot: dt * photo, sim.photo_species - 1: dt * photo}
-    _, got, _ = _euler_case(sim, True, dt, False, add=add)
+    _, got, _ = _euler_case(sim, cyl, dt, False, add=add, mask=mask)
     inner = _leaf_inner(af)
     prev = sim.tree.get_cc(sim.i_electron + 2)
-    assert not np.array_equal(got[sim.i_electron][inner], prev[inner])
+    if masked:
+        assert (inner & mask).any() and (inner & ~mask).any()
+        assert np.array_equal(got[sim.i_electron][inner & mask], prev[inner & mask])
+        assert (got[sim.i_electron][inner & ~mask] != prev[inner & ~mask]).mean() > 0.9
+    else:
+        assert not np.array_equal(got[sim.i_electron][inner], prev[inner])
     sim.tree.close()
+
+
+def test_update_with_photoionization():
+    """Mobile ions with photoionization, cylindrical and Cartesian."""
+    _photo_update(True, False)
+    _photo_update(False, False)
 
 
 def test_update_with_the_mask():
     """Cartesian, afh_fluid_set_update_mask: a cell whose level set is <= 0
     keeps the previous state for every species, ions included; the others get
-    their divergences."""
+    their divergences. Then the same with photoionization."""
+    _mask_update()
+    _photo_update(False, True)
+
+
+def _mask_update():
     sim = _sim(False, 6, reactions=False)
     af = sim.af
     dt = 1e-12
