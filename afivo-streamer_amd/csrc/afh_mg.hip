@@ -18,6 +18,7 @@
 #include <cfloat>
 #include <cmath>
 #include <map>
+#include <type_traits>
 
 #include "afh_internal.h"
 #include "afh_cs_direct.h"
@@ -97,47 +98,9 @@ __global__ void k_gsrb(double *__restrict__ phi, const double *__restrict__ rhs,
 }
 
 // ------------------------------------------------------------ fused GSRB pair
-// Half-sweeps n (odd, "red": i+j+k odd) and n+1 ("black") of gsrb_boxes
-// (m_af_multigrid.f90:741-760) in ONE pass, without the level ghost fill
-// between them; bitwise the same result as the two half-sweeps with
-// af_gc_lvl in between.
-//
-// The pair reads `src` and writes the interior of `dst` (ping-pong between
-// phi and a spare image), so every input is an old value and workgroups
-// never race. One workgroup per tile of TJ rows (j) of a box marches over
-// the k planes, holding four planes P[s-2..s+1] of its rows plus one halo
-// row on each side (and the i ghosts) in LDS. Step s:
-//   A  red cells of plane s (in-plane and k neighbours: old black values)
-//   B  the red values next to the tile that af_gc_lvl / the neighbouring
-//      tile would provide after the red half-sweep: x ghosts of the tile's
-//      rows; the halo rows (ghost row of the box, or the red cells of the
-//      adjacent tile recomputed from `src`); the z ghost planes at s = 2 and
-//      s = NC+1. A same-level neighbour's red boundary cell is recomputed
-//      from that neighbour's `src` (bitwise what its workgroup computes);
-//      physical / refinement faces use gc_face_nocopy with the box's current
-//      red and black values (coarse data from `coarse`, i.e. phi).
-//   C  black cells of plane s-1 (new red neighbours); plane s-1 of the tile
-//      is complete and written once, in full rows
-//   D  plane s+2 (prefetched into registers during the step) -> LDS
-// Each plane of phi and rhs is read once and phi is written once per pair
-// (24 B/cell algorithmic).
-template <int NC, int TJ_ = NC>
-struct RbGeom {
-  static constexpr int NG = NC + 2;
-  // rows per tile: whole boxes on levels with a box per CU (measured on
-  // MI355X, S1-64 leaf level: 16-row tiles of 1024 threads 1.06 ms per pair,
-  // whole boxes 0.87 ms -- the tiles' halo rows cost more than the extra
-  // occupancy gains); NC/4-row tiles on levels with 64..255 boxes
-  static constexpr int TJ = TJ_;
-  static constexpr int NTILE = NC / TJ;
-  static constexpr int PLT = (TJ + 2) * NG;            // LDS plane (rows j0-1..j1+1)
-  static constexpr int NT = NC * TJ >= 1024 ? 1024 : (NC * TJ < 64 ? 64 : NC * TJ);
-  static constexpr int CPT = (NC * TJ + NT - 1) / NT;  // columns per thread
-  static constexpr int EPT = (PLT + NT - 1) / NT;      // plane entries per thread
-};
-
-// One red ghost cell p of face nb for k_gsrb_pair. x1v / x2v: this box's
-// current values next to the face (x1 black, old; x2 red, new).
+// One red ghost cell p of face nb for the fused pairs (k_gsrb_pair2,
+// k_gsrb_pair_box). x1v / x2v: this box's current values next to the face
+// (x1 black, old; x2 red, new).
 template <int NC>
 __device__ __forceinline__ double pair_ghost_k(
     const double *__restrict__ src, const double *__restrict__ coarse,
@@ -171,187 +134,6 @@ __device__ __forceinline__ double pair_ghost_k(
                           [&](const int *q) { return q[d] == x1 ? x1v : x2v; });
 }
 
-template <int NC>
-__device__ __forceinline__ double pair_ghost(
-    const double *__restrict__ src, const double *__restrict__ coarse,
-    const double *__restrict__ rhs,
-    const afh_box_meta *__restrict__ meta, const afh_box_meta &m, int nb,
-    int p0, int p1, int p2, int a, int b, size_t bsz, const Coef &cf,
-    double inv_c1, afh_bc bc, int rb, double x1v, double x2v) {
-  return pair_ghost_k<NC>(src, coarse, rhs, meta, m, nb, m.neighbors[nb - 1],
-                          m.dr[(nb - 1) >> 1], p0, p1, p2, a, b, bsz, cf, inv_c1, bc,
-                          rb, x1v, x2v);
-}
-
-template <int NC, int TJ>
-__global__ void __launch_bounds__((RbGeom<NC, TJ>::NT)) __attribute__((amdgpu_waves_per_eu(4)))
-    k_gsrb_pair(const double *__restrict__ src, double *__restrict__ dst,
-                const double *__restrict__ rhs,
-                const double *__restrict__ coarse,
-                const afh_box_meta *__restrict__ meta,
-                const int32_t *__restrict__ ids, size_t bsz, Coef cf,
-                double inv_c1, GcArgs ga) {
-  using G = RbGeom<NC, TJ>;
-  constexpr int NG = G::NG, HN = NC / 2, NT = G::NT, CPT = G::CPT,
-                EPT = G::EPT, PLT = G::PLT;
-  constexpr size_t SK = (size_t)NG * NG;
-  __shared__ double P[4][PLT];  // planes s-2 .. s+1 at slot (plane & 3)
-  const int tid = threadIdx.x;
-  const int id = ids[blockIdx.x / G::NTILE];
-  const int j0 = (blockIdx.x % G::NTILE) * TJ + 1, j1 = j0 + TJ - 1;
-  const afh_box_meta &m = meta[id - 1];
-  const double *x = src + (size_t)(id - 1) * bsz;
-  double *y = dst + (size_t)(id - 1) * bsz;
-  const double *r = rhs + (size_t)(id - 1) * bsz;
-  const size_t t0 = (size_t)(j0 - 1) * NG;  // first LDS row in a plane
-  // tile column q of this thread: (i, j), LDS index c (row j - j0 + 1)
-  auto colof = [&](int q, int &i, int &j, int &c) {
-    const int col = tid + NT * q;
-    i = col % NC + 1;
-    j = j0 + col / NC;
-    c = (col / NC + 1) * NG + i;
-    return col < NC * TJ;
-  };
-
-  // planes 0..2 -> LDS; rhs of plane 1 -> registers
-  for (int e = tid; e < 3 * PLT; e += NT)
-    P[e / PLT][e % PLT] = x[(size_t)(e / PLT) * SK + t0 + e % PLT];
-  double r1[CPT], r2[CPT];
-#pragma unroll
-  for (int q = 0; q < CPT; q++) {
-    int i, j, c;
-    colof(q, i, j, c);
-    r1[q] = 0;
-    r2[q] = colof(q, i, j, c) ? r[SK + j * NG + i] : 0.0;
-  }
-  __syncthreads();
-
-  for (int s = 1; s <= NC + 1; s++) {
-    // prefetch plane s+2 of phi and the tile of plane s+1 of rhs
-    double nx[EPT], nr[CPT];
-#pragma unroll
-    for (int q = 0; q < EPT; q++) {
-      const int e = tid + NT * q;
-      nx[q] = (s + 2 <= NC + 1 && e < PLT) ? x[(size_t)(s + 2) * SK + t0 + e]
-                                            : 0.0;
-    }
-#pragma unroll
-    for (int q = 0; q < CPT; q++) {
-      int i, j, c;
-      const bool ok = colof(q, i, j, c);
-      nr[q] = (ok && s + 1 <= NC) ? r[(size_t)(s + 1) * SK + j * NG + i] : 0.0;
-    }
-    double *Pm = P[(s - 1) & 3], *P0 = P[s & 3], *Pp = P[(s + 1) & 3];
-    double *Pmm = P[(s - 2) & 3];
-    // A: red cells of plane s
-    if (s <= NC) {
-#pragma unroll
-      for (int q = 0; q < CPT; q++) {
-        int i, j, c;
-        if (colof(q, i, j, c) && ((i + j + s) & 1))
-          P0[c] = (r2[q] - cf.c[1] * P0[c - 1] - cf.c[2] * P0[c + 1] -
-                   cf.c[3] * P0[c - NG] - cf.c[4] * P0[c + NG] -
-                   cf.c[5] * Pm[c] - cf.c[6] * Pp[c]) *
-                  inv_c1;
-      }
-    }
-    __syncthreads();
-    // B: red values around the tile
-    if (s <= NC) {
-      for (int u = tid; u < TJ + NC; u += NT) {
-        int i, j, jl;
-        double v;
-        if (u < TJ) {
-          // x ghosts of the tile's rows
-          j = j0 + u;
-          jl = u + 1;
-          i = ((j + s) & 1) ? 0 : NC + 1;
-          const int nb = i == 0 ? 1 : 2;
-          v = pair_ghost<NC>(src, coarse, rhs, meta, m, nb, i, j, s, j, s, bsz,
-                             cf, inv_c1, ga.bc[nb - 1], ga.rb,
-                             P0[jl * NG + (i == 0 ? 1 : NC)],
-                             P0[jl * NG + (i == 0 ? 2 : NC - 1)]);
-        } else {
-          // halo rows j0-1 and j1+1
-          const bool lo = u - TJ < HN;
-          j = lo ? j0 - 1 : j1 + 1;
-          jl = lo ? 0 : TJ + 1;
-          i = 2 - ((1 ^ (s + j)) & 1) + 2 * ((u - TJ) % HN);
-          if (j == 0 || j == NC + 1) {
-            const int nb = j == 0 ? 3 : 4;
-            const int l1 = j == 0 ? 1 : TJ, l2 = j == 0 ? 2 : TJ - 1;
-            v = pair_ghost<NC>(src, coarse, rhs, meta, m, nb, i, j, s, i, s,
-                               bsz, cf, inv_c1, ga.bc[nb - 1], ga.rb,
-                               P0[l1 * NG + i], P0[l2 * NG + i]);
-          } else {
-            // red cell of the adjacent tile of this box
-            v = gs_cell(x, r, ix3(NG, i, j, s), NG, SK, cf, inv_c1);
-          }
-        }
-        P0[jl * NG + i] = v;
-      }
-    }
-    if (s == 2 || s == NC + 1) {
-      // z ghost plane 0 (NC+1): x1 = plane 1 (NC), black, old;
-      // x2 = plane 2 (NC-1), red, new
-      const int nb = s == 2 ? 5 : 6, k = s == 2 ? 0 : NC + 1;
-      double *Pg = s == 2 ? Pmm : P0;
-      const double *X2 = s == 2 ? P0 : Pmm;
-#pragma unroll
-      for (int q = 0; q < CPT; q++) {
-        int i, j, c;
-        if (colof(q, i, j, c) && ((i + j + k) & 1))
-          Pg[c] = pair_ghost<NC>(src, coarse, rhs, meta, m, nb, i, j, k, i, j,
-                                 bsz, cf, inv_c1, ga.bc[nb - 1], ga.rb, Pm[c],
-                                 X2[c]);
-      }
-    }
-    __syncthreads();
-    // C: black cells of plane s-1; write the tile of plane s-1
-    if (s >= 2) {
-      const int k = s - 1;
-#pragma unroll
-      for (int q = 0; q < CPT; q++) {
-        int i, j, c;
-        if (!colof(q, i, j, c)) continue;
-        const size_t g = (size_t)k * SK + (size_t)j * NG + i;
-        if (!((i + j + k) & 1)) {
-          const double v =
-              (r1[q] - cf.c[1] * Pm[c - 1] - cf.c[2] * Pm[c + 1] -
-               cf.c[3] * Pm[c - NG] - cf.c[4] * Pm[c + NG] - cf.c[5] * Pmm[c] -
-               cf.c[6] * P0[c]) *
-              inv_c1;
-          y[g] = v;
-        } else {
-          y[g] = Pm[c];
-        }
-      }
-    }
-    __syncthreads();
-    // D: plane s+2 into the slot of plane s-2
-    if (s + 2 <= NC + 1) {
-#pragma unroll
-      for (int q = 0; q < EPT; q++) {
-        const int e = tid + NT * q;
-        if (e < PLT) P[(s + 2) & 3][e] = nx[q];
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < CPT; q++) {
-      r1[q] = r2[q];
-      r2[q] = nr[q];
-    }
-    __syncthreads();
-  }
-}
-
-// Whole-box form of k_gsrb_pair with a parity mapping: in step s thread t
-// owns the same RPT (i, j) columns for the red cells of plane s (phase A)
-// and the black cells of plane s-1 (phase C) -- i = 2 ih + 1 + ((j + s) & 1)
-// -- so every lane works in both phases (the column mapping of k_gsrb_pair
-// idles half the lanes in each). Black cells are updated in place in LDS and
-// plane s-1 is then written in full rows (phase E). Same arithmetic in the
-// same order as k_gsrb_pair: bitwise identical results.
 #ifndef AFH_PAIR_NB_LOADS  // 1: every neighbour value of phase B from global
 #define AFH_PAIR_NB_LOADS 0
 #endif
@@ -370,15 +152,36 @@ struct RbPar {
   static constexpr int OPTF = (NG * TJ + NT - 1) / NT;      // same, rows with x ghosts
 };
 
-// Parity-mapped form of k_gsrb_pair: in step s thread t owns the same RPT
-// (i, j) columns for the red cells of plane s (phase A) and the black cells
-// of plane s-1 (phase C) -- i = 2 ih + 1 + ((j + s) & 1) -- so every lane
-// works in both phases (the column mapping of k_gsrb_pair idles half the
-// lanes in each). Black cells are updated in place in LDS and plane s-1 is
-// then written in full rows (phase E). A workgroup holds TJ rows of a box
-// (TJ < NC: 512-thread workgroups, two per CU, halo rows recomputed as in
-// k_gsrb_pair). Same arithmetic in the same order as k_gsrb_pair: bitwise
-// identical results.
+// Half-sweeps n (odd, "red": i+j+k odd) and n+1 ("black") of gsrb_boxes
+// (m_af_multigrid.f90:741-760) in ONE pass, without the level ghost fill
+// between them; bitwise the same result as the two half-sweeps with
+// af_gc_lvl in between.
+//
+// The pair reads `src` and writes `dst` (ping-pong between phi and a spare
+// image), so every input is an old value and workgroups never race. One
+// workgroup per tile of TJ rows (j) of a box (TJ < NC: 512-thread
+// workgroups, two per CU) marches over the k planes, holding four planes
+// P[s-2..s+1] of its rows plus one halo row on each side (and the i ghosts)
+// in LDS. Step s:
+//   A  red cells of plane s (in-plane and k neighbours: old black values)
+//   B  the red values next to the tile that af_gc_lvl / the neighbouring
+//      tile would provide after the red half-sweep: x ghosts of the tile's
+//      rows; the halo rows (ghost row of the box, or the red cells of the
+//      adjacent tile recomputed from `src`); the z ghost planes at s = 2 and
+//      s = NC+1. A same-level neighbour's red boundary cell is recomputed
+//      from that neighbour's `src` (bitwise what its workgroup computes);
+//      physical / refinement faces use gc_face_nocopy with the box's current
+//      red and black values (coarse data from `coarse`, i.e. phi).
+//   C  black cells of plane s-1 (new red neighbours), in place in LDS
+//   D  plane s+2 (prefetched into registers during the step) -> LDS
+//   E  plane s-2 of the tile, complete since step s-1, written once in full
+//      rows (with A)
+// Each plane of phi and rhs is read once and phi is written once per pair
+// (24 B/cell algorithmic).
+// Parity mapping: in step s thread t owns the same RPT (i, j) columns for
+// the red cells of plane s (A) and the black cells of plane s-1 (C) --
+// i = 2 ih + 1 + ((j + s) & 1) -- so every lane works in both phases (one
+// thread per column would idle half the lanes in each).
 // DEPTH: planes of phi / rhs in flight per workgroup (1: loaded and stored
 // in the same step; 2: loaded one step earlier). Plane rows are stored
 // whole, x ghost cells included (one contiguous run per tile plane, no
@@ -639,7 +442,7 @@ __global__ void __launch_bounds__((RbPar<NC, TJ>::NT))
     __syncthreads();
     // B: red values around the tile: x ghost cells of its rows; the halo
     // rows (ghost row of the box, or the red cells of the adjacent tile
-    // recomputed from src) -- same arithmetic as pair_ghost / gs_cell
+    // recomputed from src) -- same arithmetic as pair_ghost_k / gs_cell
     if (b_nb) {
       double v;
       if (b_pre) {
@@ -1246,6 +1049,36 @@ __device__ __forceinline__ double apply7(const double *x, size_t c, size_t sj,
          cf.c[6] * x[c + sk];
 }
 
+// The operator of a launch, passed by value: StConst, the level's constant
+// 7-point stencil, or StVar, the variable stencils of the electrode boxes.
+// Boxes the electrode surface crosses carry mg_box_lsf_stencil's
+// (m_af_multigrid.f90:1762-1834) v(7, nc^3), coefficients fastest as afivo
+// stores them, and bc_correction(nc^3) (f times the electrode potential,
+// mg_set_operators_lvl 1156-1160); vp / bp index them by box id (bp null: no
+// correction). The host launches every operation on the constant boxes of a
+// level and then on its (few) electrode boxes (const_then_var).
+// apply: L phi at cell c of the box image x (strides 1, sj, sk), which is
+// cell cv = (i-1) + nc ((j-1) + nc (k-1)) of box id; StVar subtracts
+// bc_correction (residual = rhs - (L phi - bc_correction)).
+struct StConst {
+  Coef cf;
+  __device__ double apply(int, size_t, const double *x, size_t c, size_t sj, size_t sk) const {
+    return apply7(x, c, sj, sk, cf);
+  }
+};
+
+struct StVar {
+  const double *const *vp, *const *bp;
+  __device__ double apply(int id, size_t cv, const double *x, size_t c, size_t sj,
+                          size_t sk) const {
+    const double *v = vp[id - 1] + 7 * cv, *b = bp[id - 1];
+    double a = v[0] * x[c] + v[1] * x[c - 1] + v[2] * x[c + 1] + v[3] * x[c - sj] +
+               v[4] * x[c + sj] + v[5] * x[c - sk] + v[6] * x[c + sk];
+    if (b) a = a - b[cv];
+    return a;
+  }
+};
+
 // residual_box; with MAX (leaf boxes) the max |residual| is folded into
 // shard slots (af_tree_maxabs_cc(i_tmp) of field_compute). Each thread
 // takes a column of K cells along k: the z neighbours are shared and all
@@ -1253,6 +1086,10 @@ __device__ __forceinline__ double apply7(const double *x, size_t c, size_t sj,
 // GRAD (afh_mg_set_gradient_output): the same phi values also give |E| of
 // field_from_potential's gradient (k_gradient_t's expressions, fac / dr of
 // the box), stored in nrm -- one read of phi for both.
+// (Not a template over the stencil policy: with StConst in place of the
+// Coef the columns of 4 and 8 came out with other register counts, 62 -> 56
+// up to 114 -> 76 VGPRs, and these are the measured instantiations; the
+// electrode boxes keep k_residual_v, one cell per thread, below.)
 template <bool MAX, int K, bool GRAD = false>
 __global__ void __launch_bounds__(256)
     k_residual(const double *__restrict__ phi, const double *__restrict__ rhs,
@@ -1312,12 +1149,15 @@ __global__ void __launch_bounds__(256)
   if (MAX) block_max_to_shard(mx, red);
 }
 
+// update_coarse part 1, one thread per parent cell (the column form below
+// serves the constant boxes whose size allows it)
+template <class St>
 __global__ void k_rstr_fas(double *__restrict__ phi,
                            const double *__restrict__ rhs,
                            double *__restrict__ tmp,
                            const afh_box_meta *__restrict__ meta,
                            const int32_t *__restrict__ ids, int nc, size_t bsz,
-                           Coef cf) {
+                           St st) {
   const int hn = nc >> 1;
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= hn * hn * hn) return;
@@ -1330,16 +1170,20 @@ __global__ void k_rstr_fas(double *__restrict__ phi,
   const size_t o = (size_t)(id - 1) * bsz;
   const double *x = phi + o, *r = rhs + o;
   const int fi = 2 * i - 1, fj = 2 * j - 1, fk = 2 * k - 1;
-  size_t cs[8] = {ix3(ng, fi, fj, fk),         ix3(ng, fi + 1, fj, fk),
-                  ix3(ng, fi, fj + 1, fk),     ix3(ng, fi + 1, fj + 1, fk),
-                  ix3(ng, fi, fj, fk + 1),     ix3(ng, fi + 1, fj, fk + 1),
-                  ix3(ng, fi, fj + 1, fk + 1), ix3(ng, fi + 1, fj + 1, fk + 1)};
-  double sr = r[cs[0]] - apply7(x, cs[0], sj, sk, cf);
-  double sp = x[cs[0]];
+  double sr = 0.0, sp = 0.0;
 #pragma unroll
-  for (int q = 1; q < 8; q++) {
-    sr += r[cs[q]] - apply7(x, cs[q], sj, sk, cf);
-    sp += x[cs[q]];
+  for (int q = 0; q < 8; q++) {
+    const int ci = fi + (q & 1), cj = fj + ((q >> 1) & 1), ck = fk + (q >> 2);
+    const size_t c = ix3(ng, ci, cj, ck);
+    const size_t cv = ((size_t)(ck - 1) * nc + (cj - 1)) * nc + (ci - 1);
+    const double res = r[c] - st.apply(id, cv, x, c, sj, sk);
+    if (q == 0) {
+      sr = res;
+      sp = x[c];
+    } else {
+      sr += res;
+      sp += x[c];
+    }
   }
   const size_t po = (size_t)(m.parent - 1) * bsz +
                     ix3(ng, ((m.ix[0] - 1) & 1) * hn + i,
@@ -1430,23 +1274,33 @@ __global__ void __launch_bounds__(256)
   }
 }
 
-__global__ void k_parent_rhs(const double *__restrict__ phi,
-                             double *__restrict__ rhs, double *__restrict__ tmp,
-                             const int32_t *__restrict__ ids, int nc,
-                             size_t bsz, Coef cf) {
+// update_coarse part 2 at cell t (ghost layer included) of parent box id
+template <class St>
+__device__ __forceinline__ void parent_rhs_cell(const double *phi, double *rhs, double *tmp,
+                                                int id, int t, int nc, size_t bsz,
+                                                const St &st) {
   const int ng = nc + 2;
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= ng * ng * ng) return;
-  const int id = ids[blockIdx.y];
   int i, j, k;
   cell3g(t, ng, i, j, k);
   const size_t o = (size_t)(id - 1) * bsz, c = ix3(ng, i, j, k);
+  const size_t cv = ((size_t)(k - 1) * nc + (j - 1)) * nc + (i - 1);
   // (the old rhs is read on the ghost layer only: 8 B per interior cell less)
   const double rv = (i >= 1 && i <= nc && j >= 1 && j <= nc && k >= 1 && k <= nc)
-                        ? apply7(phi + o, c, ng, (size_t)ng * ng, cf)
+                        ? st.apply(id, cv, phi + o, c, ng, (size_t)ng * ng)
                         : rhs[o + c];
   rhs[o + c] = rv + tmp[o + c];
   tmp[o + c] = phi[o + c];
+}
+
+template <class St>
+__global__ void k_parent_rhs(const double *__restrict__ phi,
+                             double *__restrict__ rhs, double *__restrict__ tmp,
+                             const int32_t *__restrict__ ids, int nc,
+                             size_t bsz, St st) {
+  const int ng = nc + 2;
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= ng * ng * ng) return;
+  parent_rhs_cell(phi, rhs, tmp, ids[blockIdx.y], t, nc, bsz, st);
 }
 
 // After k_rstr_box (faces pushed): a parent box's edges and corners, then
@@ -1462,32 +1316,38 @@ __global__ void __launch_bounds__(NT)
   const int id = ids[xcd_swizzle(blockIdx.x, gridDim.x)];
   box_edges_corners(phi, meta[id - 1], id, nc, bsz, threadIdx.x, NT);
   const int ng = nc + 2;
-  const size_t o = (size_t)(id - 1) * bsz;
-  for (int t = threadIdx.x; t < ng * ng * ng; t += NT) {
-    int i, j, k;
-    cell3g(t, ng, i, j, k);
-    const size_t c = ix3(ng, i, j, k);
-    const double rv = (i >= 1 && i <= nc && j >= 1 && j <= nc && k >= 1 && k <= nc)
-                          ? apply7(phi + o, c, ng, (size_t)ng * ng, cf)
-                          : rhs[o + c];
-    rhs[o + c] = rv + tmp[o + c];
-    tmp[o + c] = phi[o + c];
-  }
+  for (int t = threadIdx.x; t < ng * ng * ng; t += NT)
+    parent_rhs_cell(phi, rhs, tmp, id, t, nc, bsz, StConst{cf});
 }
 
 // ------------------------------------------------------------ electrode boxes
-// Boxes the electrode surface crosses carry a variable 7-point stencil
-// (mg_box_lsf_stencil, m_af_multigrid.f90:1762-1834): v(7, nc^3),
-// coefficients fastest as afivo stores them, and bc_correction(nc^3) (f times
-// the electrode potential, mg_set_operators_lvl 1156-1160); vp / bp index
-// them by box id (bp null: no correction). These kernels run on the lists of
-// such boxes only (one thread per cell; the boxes are few), the constant
-// kernels on the rest of each level.
-__device__ __forceinline__ double apply7v(const double *x, size_t c, size_t sj,
-                                          size_t sk, const double *v) {
-  return v[0] * x[c] + v[1] * x[c - 1] + v[2] * x[c + 1] + v[3] * x[c - sj] +
-         v[4] * x[c + sj] + v[5] * x[c - sk] + v[6] * x[c + sk];
+// The restriction and the parents' rhs of the boxes with a variable stencil
+// are the kernels above with StVar. The residual keeps a kernel of its own
+// (see k_residual), and so does the half-sweep: it makes the rhs round trip
+// on every cell, one thread per cell, where k_gsrb maps its threads to the
+// half-sweep's cells only.
+// residual_box with the variable stencil: tmp = rhs - (L phi - bc_correction)
+template <bool MAX>
+__global__ void k_residual_v(const double *__restrict__ phi,
+                             const double *__restrict__ rhs,
+                             double *__restrict__ tmp,
+                             const int32_t *__restrict__ ids, int nc, size_t bsz,
+                             StVar st, unsigned long long *red) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  double mx = 0.0;
+  if (t < nc * nc * nc) {
+    const int id = ids[blockIdx.y];
+    int i, j, k;
+    cell3(t, nc, i, j, k);
+    const int ng = nc + 2;
+    const size_t o = (size_t)(id - 1) * bsz, c = ix3(ng, i, j, k);
+    const double v = rhs[o + c] - st.apply(id, t, phi + o, c, ng, (size_t)ng * ng);
+    tmp[o + c] = v;
+    mx = fmax(mx, fabs(v));
+  }
+  if (MAX) block_max_to_shard(mx, red);
 }
+
 
 // stencil_gsrb_357, variable branch (m_af_stencil.f90:836-841, 958-978):
 // rhs + bc_correction on every cell, the (i+j+k+redblack) even cells
@@ -1531,100 +1391,6 @@ __global__ void k_rhs_roundtrip(double *__restrict__ rhs, const int32_t *__restr
   double v = *r;
   for (int q = 0; q < n; q++) v = (v + b[t]) - b[t];
   *r = v;
-}
-
-// residual_box with the variable stencil: tmp = rhs - (L phi - bc_correction)
-template <bool MAX>
-__global__ void k_residual_v(const double *__restrict__ phi,
-                             const double *__restrict__ rhs,
-                             double *__restrict__ tmp,
-                             const int32_t *__restrict__ ids, int nc, size_t bsz,
-                             const double *const *__restrict__ vp,
-                             const double *const *__restrict__ bp,
-                             unsigned long long *red) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  double mx = 0.0;
-  if (t < nc * nc * nc) {
-    const int id = ids[blockIdx.y];
-    int i, j, k;
-    cell3(t, nc, i, j, k);
-    const int ng = nc + 2;
-    const size_t o = (size_t)(id - 1) * bsz, c = ix3(ng, i, j, k);
-    double a = apply7v(phi + o, c, ng, (size_t)ng * ng, vp[id - 1] + 7 * (size_t)t);
-    if (bp[id - 1]) a = a - bp[id - 1][t];
-    const double v = rhs[o + c] - a;
-    tmp[o + c] = v;
-    mx = fmax(mx, fabs(v));
-  }
-  if (MAX) block_max_to_shard(mx, red);
-}
-
-// k_rstr_fas for children with a variable stencil
-__global__ void k_rstr_fas_v(double *__restrict__ phi,
-                             const double *__restrict__ rhs,
-                             double *__restrict__ tmp,
-                             const afh_box_meta *__restrict__ meta,
-                             const int32_t *__restrict__ ids, int nc, size_t bsz,
-                             const double *const *__restrict__ vp,
-                             const double *const *__restrict__ bp) {
-  const int hn = nc >> 1;
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= hn * hn * hn) return;
-  const int id = ids[blockIdx.y];
-  const afh_box_meta &m = meta[id - 1];
-  int i, j, k;
-  cell3(t, hn, i, j, k);
-  const int ng = nc + 2;
-  const size_t sj = ng, sk = (size_t)ng * ng;
-  const size_t o = (size_t)(id - 1) * bsz;
-  const double *x = phi + o, *r = rhs + o, *v = vp[id - 1], *b = bp[id - 1];
-  const int fi = 2 * i - 1, fj = 2 * j - 1, fk = 2 * k - 1;
-  double sr = 0.0, sp = 0.0;
-#pragma unroll
-  for (int q = 0; q < 8; q++) {
-    const int ci = fi + (q & 1), cj = fj + ((q >> 1) & 1), ck = fk + (q >> 2);
-    const size_t c = ix3(ng, ci, cj, ck);
-    const size_t cv = ((size_t)(ck - 1) * nc + (cj - 1)) * nc + (ci - 1);
-    double a = apply7v(x, c, sj, sk, v + 7 * cv);
-    if (b) a = a - b[cv];
-    const double res = r[c] - a;
-    if (q == 0) {
-      sr = res;
-      sp = x[c];
-    } else {
-      sr += res;
-      sp += x[c];
-    }
-  }
-  const size_t po = (size_t)(m.parent - 1) * bsz +
-                    ix3(ng, ((m.ix[0] - 1) & 1) * hn + i,
-                        ((m.ix[1] - 1) & 1) * hn + j,
-                        ((m.ix[2] - 1) & 1) * hn + k);
-  tmp[po] = 0.125 * sr;
-  phi[po] = 0.125 * sp;
-}
-
-// k_parent_rhs for parents with a variable stencil
-__global__ void k_parent_rhs_v(const double *__restrict__ phi,
-                               double *__restrict__ rhs, double *__restrict__ tmp,
-                               const int32_t *__restrict__ ids, int nc, size_t bsz,
-                               const double *const *__restrict__ vp,
-                               const double *const *__restrict__ bp) {
-  const int ng = nc + 2;
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= ng * ng * ng) return;
-  const int id = ids[blockIdx.y];
-  int i, j, k;
-  cell3g(t, ng, i, j, k);
-  const size_t o = (size_t)(id - 1) * bsz, c = ix3(ng, i, j, k);
-  double rv = rhs[o + c];
-  if (i >= 1 && i <= nc && j >= 1 && j <= nc && k >= 1 && k <= nc) {
-    const size_t cv = ((size_t)(k - 1) * nc + (j - 1)) * nc + (i - 1);
-    rv = apply7v(phi + o, c, ng, (size_t)ng * ng, vp[id - 1] + 7 * cv);
-    if (bp[id - 1]) rv = rv - bp[id - 1][cv];
-  }
-  rhs[o + c] = rv + tmp[o + c];
-  tmp[o + c] = phi[o + c];
 }
 
 // Level-1 electrode solve: copy of phi (compact, one slot per level-1 box),
@@ -2802,11 +2568,11 @@ struct afh_mg {
   // stays with its tree, whose flags never change (afh_tree_regrid makes a
   // new tree with the same flags, and new multigrids with it)
   int tab_bc[6] = {0, 0, 0, 0, 0, 0};
-  // fused GSRB pairs (k_gsrb_pair) on levels with at least fused_min boxes
-  // (default: enough boxes for one workgroup per CU, 256 tiles)
+  // fused GSRB pairs (k_gsrb_pair_box, k_gsrb_pair2) on levels with at least
+  // fused_min boxes (default: every level of boxes up to 16^3, from 64 boxes
+  // for the plane march of 32^3 and 64^3; AFH_GSRB_FUSED_MIN_BOXES)
   int fused_min = 0;
   bool force_tiles = false;  // AFH_GSRB_TILES
-  bool pair_box = true;      // false: plane-marching pair for NC <= 16
   // AFH_RCCL_CAPTURE=1: a V-cycle of a tree sharded over RCCL is captured as
   // ONE graph with its exchanges (pack, grouped send / recv, unpack) inside,
   // instead of segments between host-driven exchanges. Off until measured on
@@ -3151,7 +2917,7 @@ int32_t afh_mg_create(afh_tree *t, const afh_mg_desc *d, afh_mg **out) {
     // level: the small levels are launch-bound (S1 0.768 -> 0.737 ms/step,
     // S3 2.57 -> 2.54, scripts/env_bench_ab.sh); bitwise the split form
     // (test_3d every row, scripts/rtest_determinism.py)
-    mg->fused_min = t->nc >= 32 ? 64 : (t->nc <= 16 && mg->pair_box ? 1 : 256);
+    mg->fused_min = t->nc >= 32 ? 64 : 1;
   if (const char *env = getenv("AFH_GSRB_TILES")) mg->force_tiles = atoi(env) != 0;
   if (const char *env = getenv("AFH_GRAPHS")) mg->use_graphs = atoi(env) != 0;
   if (const char *env = getenv("AFH_RSTR_COL")) mg->rstr_col = atoi(env) != 0;
@@ -3261,17 +3027,30 @@ static void launch_ev(K k, hipEvent_t e0, hipEvent_t e1, dim3 g, dim3 b,
     hipLaunchKernelGGL(k, g, b, 0, st, a...);
 }
 
-template <int NC, int TJ>
-static void launch_pair_t(afh_mg *mg, int lvl, const double *src, double *dst,
-                          const Coef &cf, double inv_c1, hipEvent_t e0, hipEvent_t e1) {
-  afh_tree *t = mg->t;
-  launch_ev((k_gsrb_pair<NC, TJ>), e0, e1,
-                     dim3(t->ids.n(lvl) * RbGeom<NC, TJ>::NTILE),
-                     dim3(RbGeom<NC, TJ>::NT), t->stream, src, dst,
-                     t->ccv(mg->d.i_rhs), t->ccv(mg->d.i_phi), t->d_boxes,
-                     t->ids.at(lvl), t->bsz, cf, inv_c1,
-                     t->gc_args(mg->d.i_phi));
+// A run-time size as a template argument: f(Int<N>{}) for the N of the list
+// that equals n; false when none does (the caller's generic kernel, if any).
+template <int N> using Int = std::integral_constant<int, N>;
+template <int... Ns, class F> static bool with_size(int n, F &&f) {
+  return ((n == Ns ? (f(Int<Ns>{}), true) : false) || ...);
 }
+// the box sizes with kernels of their own, and the column lengths
+template <class F> static bool with_nc(int nc, F &&f) { return with_size<4, 8, 16, 32, 64>(nc, f); }
+template <class F> static bool with_col(int k, F &&f) { return with_size<8, 4, 2>(k, f); }
+template <class F> static void with_bool(bool b, F &&f) {
+  b ? f(std::true_type{}) : f(std::false_type{});
+}
+
+// One operation on a level list: f(boxes, StConst of level lvl) on its
+// constant-stencil part c (the whole list when no box has a variable
+// stencil), then f(boxes, StVar) on its electrode boxes v; f skips an empty
+// list. The first error ends it.
+template <class F>
+static int32_t const_then_var(const afh_mg *mg, int lvl, const LevelList &all,
+                              const LevelList &c, const LevelList &v, F &&f) {
+  if (int32_t e = f(mg->any_var ? c : all, StConst{mg->lvl_c[lvl - 1]})) return e;
+  return mg->any_var ? f(v, StVar{mg->d_vp, mg->d_bp}) : AFH_OK;
+}
+template <class St> constexpr bool is_var = std::is_same<St, StVar>::value;
 
 // whole boxes per workgroup, or NC/4-row tiles (NC >= 32) on levels of
 // 64..255 boxes, which fill the CUs with 4 tiles per box
@@ -3299,7 +3078,7 @@ static void launch_pair2(afh_mg *mg, int lvl, const double *src, double *dst,
 // unless the tree is sharded (a replica's ghosts are its owner's to fill,
 // through the exchange hooks) or AFH_PAIR_PUSH=0
 static bool pair_push(const afh_mg *mg) {
-  return mg->pair_push && mg->pair_box && mg->t->nc <= 16 && !mg->t->hook;
+  return mg->pair_push && mg->t->nc <= 16 && !mg->t->hook;
 }
 
 // pend: rhs round trips of earlier pairs of the leg not yet stored (read
@@ -3312,50 +3091,41 @@ static void launch_pair(afh_mg *mg, int lvl, const double *src, double *dst,
   afh_tree *t = mg->t;
   if (t->ids.n(lvl) == 0) return;
   if constexpr (NC <= 16) {
-    if (mg->pair_box) {
-      const bool var = mg->any_var && mg->lvl_var[lvl - 1];
-      auto go = [&](auto kern) {
-        launch_ev(kern, e0, e1, dim3(t->ids.n(lvl)), dim3(RbBox<NC>::NT), t->stream, src, dst,
-                  t->ccv(mg->d.i_rhs), t->ccv(mg->d.i_phi), t->d_boxes, t->ids.at(lvl),
-                  t->bsz, cf, inv_c1, t->gc_args(mg->d.i_phi),
-                  (const double *const *)mg->d_vp, (const double *const *)mg->d_bp,
-                  var ? pend : 0);
-      };
-      if (pair_push(mg))
-        var ? go(k_gsrb_pair_box<NC, true, true>) : go(k_gsrb_pair_box<NC, true>);
-      else
-        var ? go(k_gsrb_pair_box<NC, false, true>) : go(k_gsrb_pair_box<NC>);
-      if (var && mg->ids_v.n(lvl) && last) {
-        // the half-sweeps' rhs round trips on the electrode boxes: two per
-        // pair, this pair's and the pending ones, in one launch (round 6)
-        const int nc = t->nc;
-        hipLaunchKernelGGL(k_rhs_roundtrip, dim3((nc * nc * nc + 255) / 256, mg->ids_v.n(lvl)),
-                           dim3(256), 0, t->stream, t->ccv(mg->d.i_rhs), mg->ids_v.at(lvl),
-                           nc, t->bsz, (const double *const *)mg->d_bp, pend + 2);
-        // (the caller's launch check covers it)
-      }
-      return;
+    const bool var = mg->any_var && mg->lvl_var[lvl - 1];
+    auto go = [&](auto kern) {
+      launch_ev(kern, e0, e1, dim3(t->ids.n(lvl)), dim3(RbBox<NC>::NT), t->stream, src, dst,
+                t->ccv(mg->d.i_rhs), t->ccv(mg->d.i_phi), t->d_boxes, t->ids.at(lvl),
+                t->bsz, cf, inv_c1, t->gc_args(mg->d.i_phi),
+                (const double *const *)mg->d_vp, (const double *const *)mg->d_bp,
+                var ? pend : 0);
+    };
+    if (pair_push(mg))
+      var ? go(k_gsrb_pair_box<NC, true, true>) : go(k_gsrb_pair_box<NC, true>);
+    else
+      var ? go(k_gsrb_pair_box<NC, false, true>) : go(k_gsrb_pair_box<NC>);
+    if (var && mg->ids_v.n(lvl) && last) {
+      // the half-sweeps' rhs round trips on the electrode boxes: two per
+      // pair, this pair's and the pending ones, in one launch (round 6)
+      const int nc = t->nc;
+      hipLaunchKernelGGL(k_rhs_roundtrip, dim3((nc * nc * nc + 255) / 256, mg->ids_v.n(lvl)),
+                         dim3(256), 0, t->stream, t->ccv(mg->d.i_rhs), mg->ids_v.at(lvl),
+                         nc, t->bsz, (const double *const *)mg->d_bp, pend + 2);
+      // (the caller's launch check covers it)
     }
+  } else if (pair_tiles(mg, lvl)) {
+    // too few boxes for the chip: 64^3 splits the march over k, 32^3 runs
+    // quarter-box tiles. A rank's share of a sharded level can be a few
+    // boxes (S1-64's level 3 on 8 ranks: 8): 16 chunks of 4 planes then
+    // (round 6; bitwise any split)
+    if constexpr (NC == 32)
+      launch_pair2<NC, NC / 4, 2>(mg, lvl, src, dst, cf, inv_c1, e0, e1);
+    else if (t->ids.n(lvl) <= 16)
+      launch_pair2<NC, NC, 1, 16>(mg, lvl, src, dst, cf, inv_c1, e0, e1);
+    else
+      launch_pair2<NC, NC, 1, 4>(mg, lvl, src, dst, cf, inv_c1, e0, e1);
+  } else {
+    launch_pair2<NC, NC, NC == 64 ? 1 : 2>(mg, lvl, src, dst, cf, inv_c1, e0, e1);
   }
-  if constexpr (NC >= 32) {
-    if (pair_tiles(mg, lvl)) {
-      // too few boxes for the chip: 64^3 splits the march over k, 32^3 runs
-      // quarter-box tiles. A rank's share of a sharded level can be a few
-      // boxes (S1-64's level 3 on 8 ranks: 8): 16 chunks of 4 planes then
-      // (round 6; bitwise any split)
-      if constexpr (NC == 64) {
-        if (t->ids.n(lvl) <= 16)
-          return launch_pair2<NC, NC, 1, 16>(mg, lvl, src, dst, cf, inv_c1, e0, e1);
-        return launch_pair2<NC, NC, 1, 4>(mg, lvl, src, dst, cf, inv_c1, e0, e1);
-      }
-      return launch_pair2<NC, NC / 4, 2>(mg, lvl, src, dst, cf, inv_c1, e0, e1);
-    }
-  }
-  if constexpr (NC >= 16) {
-    if constexpr (NC == 64) return launch_pair2<NC, NC, 1>(mg, lvl, src, dst, cf, inv_c1, e0, e1);
-    return launch_pair2<NC, NC, 2>(mg, lvl, src, dst, cf, inv_c1, e0, e1);
-  }
-  launch_pair_t<NC, NC>(mg, lvl, src, dst, cf, inv_c1, e0, e1);
 }
 
 extern "C" {
@@ -3364,8 +3134,7 @@ extern "C" {
 // every rank of a sharded tree: decided on the level's total box count)
 static bool fused_level(const afh_mg *mg, int lvl) {
   // electrode stencils: the small-box pair has a variable form (VAR)
-  if (mg->any_var && mg->lvl_var[lvl - 1] && !(mg->pair_box && mg->t->nc <= 16))
-    return false;
+  if (mg->any_var && mg->lvl_var[lvl - 1] && mg->t->nc > 16) return false;
   return mg->alt && mg->t->lvl_total[lvl - 1] >= mg->fused_min;
 }
 
@@ -3414,35 +3183,28 @@ static int32_t prepare_var(afh_mg *mg) {
   return upload_list(t, mg->lsf_leaves, ll);
 }
 
-// the constant-stencil part of a level list (the whole list without
-// electrode boxes)
-static const LevelList &cst(const afh_mg *mg, const LevelList &all,
-                            const LevelList &c) {
-  return mg->any_var ? c : all;
-}
-
 static int32_t gsrb_half(afh_mg *mg, int lvl, int n, bool corners) {
   afh_tree *t = mg->t;
-  const LevelList &L = cst(mg, t->ids, mg->ids_c);
-  const int nid = L.n(lvl), nc = t->nc;
-  const Coef cf = mg->lvl_c[lvl - 1];
-  const int cells = nc * nc * nc / 2;
-  if (nid) {
-    prof_begin(t, AFH_PROF_GSRB);
-    hipLaunchKernelGGL(k_gsrb, dim3((cells + 255) / 256, nid), dim3(256), 0,
-                       t->stream, t->ccv(mg->d.i_phi), t->ccv(mg->d.i_rhs),
-                       L.at(lvl), nc, t->bsz, cf, 1 / cf.c[0], n);
-    // read phi (all), rhs (half), write phi (half) = 16 B/cell
-    prof_end(t, AFH_PROF_GSRB, 16.0 * nc * nc * nc * nid);
-    AFH_LAUNCH_CHECK("k_gsrb");
-  }
-  const int nv = mg->any_var ? mg->ids_v.n(lvl) : 0;
-  if (nv) {
-    hipLaunchKernelGGL(k_gsrb_v, dim3((nc * nc * nc + 255) / 256, nv), dim3(256),
-                       0, t->stream, t->ccv(mg->d.i_phi), t->ccv(mg->d.i_rhs),
-                       mg->ids_v.at(lvl), nc, t->bsz, mg->d_vp, mg->d_bp, n);
-    AFH_LAUNCH_CHECK("k_gsrb_v");
-  }
+  const int nc = t->nc, n3 = nc * nc * nc;
+  double *phi = t->ccv(mg->d.i_phi), *rhs = t->ccv(mg->d.i_rhs);
+  auto sweep = [&](const LevelList &L, auto st) -> int32_t {
+    const int nid = L.n(lvl);
+    if (!nid) return AFH_OK;
+    if constexpr (is_var<decltype(st)>) {
+      hipLaunchKernelGGL(k_gsrb_v, dim3((n3 + 255) / 256, nid), dim3(256), 0, t->stream, phi,
+                         rhs, L.at(lvl), nc, t->bsz, st.vp, st.bp, n);
+      AFH_LAUNCH_CHECK("k_gsrb_v");
+    } else {
+      prof_begin(t, AFH_PROF_GSRB);
+      hipLaunchKernelGGL(k_gsrb, dim3((n3 / 2 + 255) / 256, nid), dim3(256), 0, t->stream, phi,
+                         rhs, L.at(lvl), nc, t->bsz, st.cf, 1 / st.cf.c[0], n);
+      // read phi (all), rhs (half), write phi (half) = 16 B/cell
+      prof_end(t, AFH_PROF_GSRB, 16.0 * n3 * nid);
+      AFH_LAUNCH_CHECK("k_gsrb");
+    }
+    return AFH_OK;
+  };
+  if (int32_t e = const_then_var(mg, lvl, t->ids, mg->ids_c, mg->ids_v, sweep)) return e;
   // (a split half-sweep reads ghost cells only; a fused level's pair may
   // follow)
   return gc_lvl(t, lvl, mg->d.i_phi, corners, fused_level(mg, lvl), fused_level(mg, lvl) ? 2 : 1);
@@ -3450,7 +3212,7 @@ static int32_t gsrb_half(afh_mg *mg, int lvl, int n, bool corners) {
 
 // gsrb_boxes (m_af_multigrid.f90:741-760): 2 n_cycle half-sweeps, each
 // followed by a ghost fill of the level. On levels with enough boxes the
-// pairs run fused (k_gsrb_pair), alternating phi -> alt -> phi; an odd
+// pairs run fused (launch_pair), alternating phi -> alt -> phi; an odd
 // number of pairs starts with one split pair.
 static int32_t gsrb_boxes(afh_mg *mg, int lvl, bool up, bool stale_ghosts = false) {
   afh_tree *t = mg->t;
@@ -3499,13 +3261,9 @@ static int32_t gsrb_boxes(afh_mg *mg, int lvl, bool up, bool stale_ghosts = fals
     // after its last pair; nothing else reads the rhs in between)
     const int pend = 2 * (n - n0);
     const bool last = n == n_cycle;
-    switch (nc) {
-    case 4: launch_pair<4>(mg, lvl, src, dst, cf, inv_c1, e0, e1, pend, last); break;
-    case 8: launch_pair<8>(mg, lvl, src, dst, cf, inv_c1, e0, e1, pend, last); break;
-    case 16: launch_pair<16>(mg, lvl, src, dst, cf, inv_c1, e0, e1, pend, last); break;
-    case 32: launch_pair<32>(mg, lvl, src, dst, cf, inv_c1, e0, e1); break;
-    default: launch_pair<64>(mg, lvl, src, dst, cf, inv_c1, e0, e1); break;
-    }
+    with_nc(nc, [&](auto NC) {
+      launch_pair<decltype(NC)::value>(mg, lvl, src, dst, cf, inv_c1, e0, e1, pend, last);
+    });
     // a red+black pair reads phi and rhs and writes phi
     // once = 24 B/cell
     if (timed) prof_count(t, 24.0 * nc * nc * nc * nid);
@@ -3543,102 +3301,77 @@ static bool rstr_push(const afh_mg *mg, int lvl, bool ghosts_valid) {
 static int32_t update_coarse(afh_mg *mg, int lvl, bool ghosts_valid = false) {
   afh_tree *t = mg->t;
   const int nc = t->nc, hn = nc / 2;
-  const LevelList &L = cst(mg, t->ids, mg->ids_c);
-  const int nid = L.n(lvl);
+  double *phi = t->ccv(mg->d.i_phi), *rhs = t->ccv(mg->d.i_rhs), *tmp = t->ccv(mg->d.i_tmp);
   if (rstr_push(mg, lvl, ghosts_valid)) {
     const GcArgs ga = t->gc_args(mg->d.i_phi);
-    const Coef cf = mg->lvl_c[lvl - 1];
-    double *phi = t->ccv(mg->d.i_phi), *rhs = t->ccv(mg->d.i_rhs), *tmp = t->ccv(mg->d.i_tmp);
+    const int nid = t->ids.n(lvl), np = t->parents.n(lvl - 1);
     if (nid) {
-      if (nc == 4)
-        hipLaunchKernelGGL(k_rstr_box<4>, dim3(nid), dim3(64), 0, t->stream, phi, rhs, tmp,
-                           t->d_boxes, L.at(lvl), t->bsz, cf, ga);
-      else if (nc == 8)
-        hipLaunchKernelGGL(k_rstr_box<8>, dim3(nid), dim3(64), 0, t->stream, phi, rhs, tmp,
-                           t->d_boxes, L.at(lvl), t->bsz, cf, ga);
-      else
-        hipLaunchKernelGGL(k_rstr_box<16>, dim3(nid), dim3(512), 0, t->stream, phi, rhs, tmp,
-                           t->d_boxes, L.at(lvl), t->bsz, cf, ga);
+      with_size<4, 8, 16>(nc, [&](auto NC_) {
+        constexpr int NC = decltype(NC_)::value;
+        hipLaunchKernelGGL(k_rstr_box<NC>, dim3(nid), dim3(NC >= 16 ? 512 : 64), 0, t->stream,
+                           phi, rhs, tmp, t->d_boxes, t->ids.at(lvl), t->bsz,
+                           mg->lvl_c[lvl - 1], ga);
+      });
       AFH_LAUNCH_CHECK("k_rstr_box");
     }
-    const int np = t->parents.n(lvl - 1);
     if (np) {
-      if (nc == 16)
-        hipLaunchKernelGGL(k_parent_rhs_box<512>, dim3(np), dim3(512), 0, t->stream, phi, rhs,
+      with_bool(nc == 16, [&](auto big) {
+        constexpr int NT = decltype(big)::value ? 512 : 256;
+        hipLaunchKernelGGL(k_parent_rhs_box<NT>, dim3(np), dim3(NT), 0, t->stream, phi, rhs,
                            tmp, t->d_boxes, t->parents.at(lvl - 1), nc, t->bsz,
                            mg->lvl_c[lvl - 2]);
-      else
-        hipLaunchKernelGGL(k_parent_rhs_box<256>, dim3(np), dim3(256), 0, t->stream, phi,
-                           rhs, tmp, t->d_boxes, t->parents.at(lvl - 1), nc, t->bsz,
-                           mg->lvl_c[lvl - 2]);
+      });
       AFH_LAUNCH_CHECK("k_parent_rhs_box");
     }
     return AFH_OK;
   }
-  const double *fine = t->ccv(mg->d.i_phi);
-  if (nid) {
-    // column length (AFH_RSTR_K = 2, 4 or 8): a column reads 2K + 2 fine
-    // planes for 2K; each doubling of K halves that excess at twice the
-    // centre registers
-    // (workgroup size AFH_RSTR_BS: with 128 the blocks of neighbouring
-    // columns along k are 8 apart in dispatch order, i.e. on the same XCD,
-    // whose L2 then holds the fine plane both read)
-    const int RK = mg->rstr_k, BS = mg->rstr_bs;
-    if (mg->rstr_col && RK == 8 && hn % 8 == 0)
-      hipLaunchKernelGGL(k_rstr_fas_col<8>, dim3((hn * hn * (hn / 8) + BS - 1) / BS, nid),
-                         dim3(BS), 0, t->stream, t->ccv(mg->d.i_phi),
-                         t->ccv(mg->d.i_rhs), t->ccv(mg->d.i_tmp), t->d_boxes,
-                         L.at(lvl), nc, t->bsz, mg->lvl_c[lvl - 1], fine);
-    else if (mg->rstr_col && RK >= 4 && hn % 4 == 0)
-      hipLaunchKernelGGL(k_rstr_fas_col<4>, dim3((hn * hn * (hn / 4) + BS - 1) / BS, nid),
-                         dim3(BS), 0, t->stream, t->ccv(mg->d.i_phi),
-                         t->ccv(mg->d.i_rhs), t->ccv(mg->d.i_tmp), t->d_boxes,
-                         L.at(lvl), nc, t->bsz, mg->lvl_c[lvl - 1], fine);
-    else if (mg->rstr_col && hn % 2 == 0)
-      hipLaunchKernelGGL(k_rstr_fas_col<2>, dim3((hn * hn * (hn / 2) + BS - 1) / BS, nid),
-                         dim3(BS), 0, t->stream, t->ccv(mg->d.i_phi),
-                         t->ccv(mg->d.i_rhs), t->ccv(mg->d.i_tmp), t->d_boxes,
-                         L.at(lvl), nc, t->bsz, mg->lvl_c[lvl - 1], fine);
-    else
-      hipLaunchKernelGGL(k_rstr_fas, dim3((hn * hn * hn + 255) / 256, nid),
-                         dim3(256), 0, t->stream, t->ccv(mg->d.i_phi),
-                         t->ccv(mg->d.i_rhs), t->ccv(mg->d.i_tmp), t->d_boxes,
-                         L.at(lvl), nc, t->bsz, mg->lvl_c[lvl - 1]);
-    AFH_LAUNCH_CHECK("k_rstr_fas");
-  }
-  const int nv = mg->any_var ? mg->ids_v.n(lvl) : 0;
-  if (nv) {
-    hipLaunchKernelGGL(k_rstr_fas_v, dim3((hn * hn * hn + 255) / 256, nv),
-                       dim3(256), 0, t->stream, t->ccv(mg->d.i_phi),
-                       t->ccv(mg->d.i_rhs), t->ccv(mg->d.i_tmp), t->d_boxes,
-                       mg->ids_v.at(lvl), nc, t->bsz, mg->d_vp, mg->d_bp);
-    AFH_LAUNCH_CHECK("k_rstr_fas_v");
-  }
+  // column length (AFH_RSTR_K = 2, 4 or 8) of the constant boxes: a column
+  // reads 2K + 2 fine planes for 2K; each doubling of K halves that excess
+  // at twice the centre registers; 0: one coarse cell per thread
+  // (workgroup size AFH_RSTR_BS: with 128 the blocks of neighbouring
+  // columns along k are 8 apart in dispatch order, i.e. on the same XCD,
+  // whose L2 then holds the fine plane both read)
+  const int RK = mg->rstr_k, BS = mg->rstr_bs;
+  const int kc = !mg->rstr_col               ? 0
+                 : RK == 8 && hn % 8 == 0    ? 8
+                 : RK >= 4 && hn % 4 == 0    ? 4
+                 : hn % 2 == 0               ? 2
+                                             : 0;
+  auto rstr = [&](const LevelList &L, auto st) -> int32_t {
+    const int nid = L.n(lvl);
+    if (!nid) return AFH_OK;
+    bool col = false;
+    if constexpr (!is_var<decltype(st)>)
+      col = with_col(kc, [&](auto K_) {
+        constexpr int K = decltype(K_)::value;
+        hipLaunchKernelGGL(k_rstr_fas_col<K>, dim3((hn * hn * (hn / K) + BS - 1) / BS, nid),
+                           dim3(BS), 0, t->stream, phi, rhs, tmp, t->d_boxes, L.at(lvl), nc,
+                           t->bsz, st.cf, phi);
+      });
+    if (!col)
+      hipLaunchKernelGGL(k_rstr_fas<decltype(st)>, dim3((hn * hn * hn + 255) / 256, nid),
+                         dim3(256), 0, t->stream, phi, rhs, tmp, t->d_boxes, L.at(lvl), nc,
+                         t->bsz, st);
+    AFH_LAUNCH_CHECK(is_var<decltype(st)> ? "k_rstr_fas_v" : "k_rstr_fas");
+    return AFH_OK;
+  };
   int32_t e;
+  if ((e = const_then_var(mg, lvl, t->ids, mg->ids_c, mg->ids_v, rstr))) return e;
   if ((e = call_hook(t, AFH_HOOK_RESTRICT, lvl, mg->d.i_phi)) ||
       (e = call_hook(t, AFH_HOOK_RESTRICT, lvl, mg->d.i_tmp)))
     return e;
   if ((e = gc_lvl(t, lvl - 1, mg->d.i_phi, 1, fused_level(mg, lvl - 1),
                   fused_level(mg, lvl - 1) ? 2 : 1)))
     return e;
-  const LevelList &P = cst(mg, t->parents, mg->parents_c);
-  const int np = P.n(lvl - 1);
-  if (np) {
-    hipLaunchKernelGGL(k_parent_rhs, dim3((unsigned)((t->bsz + 255) / 256), np),
-                       dim3(256), 0, t->stream, t->ccv(mg->d.i_phi),
-                       t->ccv(mg->d.i_rhs), t->ccv(mg->d.i_tmp),
-                       P.at(lvl - 1), nc, t->bsz, mg->lvl_c[lvl - 2]);
-    AFH_LAUNCH_CHECK("k_parent_rhs");
-  }
-  const int npv = mg->any_var ? mg->parents_v.n(lvl - 1) : 0;
-  if (npv) {
-    hipLaunchKernelGGL(k_parent_rhs_v, dim3((unsigned)((t->bsz + 255) / 256), npv),
-                       dim3(256), 0, t->stream, t->ccv(mg->d.i_phi),
-                       t->ccv(mg->d.i_rhs), t->ccv(mg->d.i_tmp),
-                       mg->parents_v.at(lvl - 1), nc, t->bsz, mg->d_vp, mg->d_bp);
-    AFH_LAUNCH_CHECK("k_parent_rhs_v");
-  }
-  return AFH_OK;
+  auto parent_rhs = [&](const LevelList &P, auto st) -> int32_t {
+    const int np = P.n(lvl - 1);
+    if (!np) return AFH_OK;
+    hipLaunchKernelGGL(k_parent_rhs<decltype(st)>, dim3((unsigned)((t->bsz + 255) / 256), np),
+                       dim3(256), 0, t->stream, phi, rhs, tmp, P.at(lvl - 1), nc, t->bsz, st);
+    AFH_LAUNCH_CHECK(is_var<decltype(st)> ? "k_parent_rhs_v" : "k_parent_rhs");
+    return AFH_OK;
+  };
+  return const_then_var(mg, lvl - 1, t->parents, mg->parents_c, mg->parents_v, parent_rhs);
 }
 
 // the correction of level lvl also fills its faces (k_prolong_box): small
@@ -3661,18 +3394,12 @@ static int32_t correct_children(afh_mg *mg, int lvl) {
   const int nid = t->ids.n(lvl);
   if (nid && prolong_push(mg, lvl)) {
     const GcArgs ga = t->gc_args(mg->d.i_phi);
-    if (nc == 4)
-      hipLaunchKernelGGL(k_prolong_box<4>, dim3(nid), dim3(RbBox<4>::NT), 0, t->stream,
+    with_size<4, 8, 16>(nc, [&](auto NC_) {
+      constexpr int NC = decltype(NC_)::value;
+      hipLaunchKernelGGL(k_prolong_box<NC>, dim3(nid), dim3(RbBox<NC>::NT), 0, t->stream,
                          t->ccv(mg->d.i_phi), t->ccv(mg->d.i_tmp), t->d_boxes, t->ids.at(lvl),
                          t->bsz, ga);
-    else if (nc == 8)
-      hipLaunchKernelGGL(k_prolong_box<8>, dim3(nid), dim3(RbBox<8>::NT), 0, t->stream,
-                         t->ccv(mg->d.i_phi), t->ccv(mg->d.i_tmp), t->d_boxes, t->ids.at(lvl),
-                         t->bsz, ga);
-    else
-      hipLaunchKernelGGL(k_prolong_box<16>, dim3(nid), dim3(RbBox<16>::NT), 0, t->stream,
-                         t->ccv(mg->d.i_phi), t->ccv(mg->d.i_tmp), t->d_boxes, t->ids.at(lvl),
-                         t->bsz, ga);
+    });
     AFH_LAUNCH_CHECK("k_prolong_box");
   } else if (nid) {
     double *fphi = t->ccv(mg->d.i_phi);
@@ -3682,18 +3409,10 @@ static int32_t correct_children(afh_mg *mg, int lvl) {
     const int want = mg->prolong_k;
     const int K = want == 8 && nc % 8 == 0 ? 8 : want >= 4 && nc % 4 == 0 ? 4 : 2;
     const dim3 grid((nc * nc * (nc / K) + 255) / 256, nid);
-    if (K == 8)
-      hipLaunchKernelGGL(k_prolong<8>, grid, dim3(256), 0, t->stream,
-                         fphi, t->ccv(mg->d.i_tmp), t->d_boxes,
-                         t->ids.at(lvl), nc, t->bsz);
-    else if (K == 4)
-      hipLaunchKernelGGL(k_prolong<4>, grid, dim3(256), 0, t->stream,
-                         fphi, t->ccv(mg->d.i_tmp), t->d_boxes,
-                         t->ids.at(lvl), nc, t->bsz);
-    else
-      hipLaunchKernelGGL(k_prolong<2>, grid, dim3(256), 0, t->stream,
-                         fphi, t->ccv(mg->d.i_tmp), t->d_boxes,
-                         t->ids.at(lvl), nc, t->bsz);
+    with_col(K, [&](auto K_) {
+      hipLaunchKernelGGL(k_prolong<decltype(K_)::value>, grid, dim3(256), 0, t->stream, fphi,
+                         t->ccv(mg->d.i_tmp), t->d_boxes, t->ids.at(lvl), nc, t->bsz);
+    });
     AFH_LAUNCH_CHECK("k_prolong");
   }
   return AFH_OK;
@@ -4327,53 +4046,49 @@ static int32_t residual_levels(afh_mg *mg, int max_lvl, bool max_out) {
   // the constant-coefficient boxes of every level in one launch per part
   // (the level's coefficients from d_lvl_c): levels do not interact here
   const bool all_lvls = t->all_lvl_launch;
+  const bool gr = grad_fused(mg, max_lvl);
+  // columns of 8 on the large boxes: 693 against 728 us per 64^3 leaf
+  // launch (profiles/r03_ab_res_k.txt); small boxes keep their threads
+  const int rk = mg->res_k ? mg->res_k : nc >= 32 ? 8 : 4;
+  const int kc = nc % rk == 0 ? rk : nc % 4 == 0 ? 4 : 2;
   for (int lvl = 1; lvl <= max_lvl; lvl++) {
-    const Coef &cf = mg->lvl_c[lvl - 1];
     for (int part = 0; part < 2; part++) {
       // part 0: leaves (max folded), part 1: parents; without max_out the
       // level's whole id list in one launch
       if (!max_out && part) break;
-      const LevelList &A = max_out ? (part ? t->parents : t->leaves) : t->ids;
-      const LevelList &Lc = max_out ? (part ? mg->parents_c : mg->leaves_c) : mg->ids_c;
-      const LevelList &Lv = max_out ? (part ? mg->parents_v : mg->leaves_v) : mg->ids_v;
-      const LevelList &L = cst(mg, A, Lc);
-      const int n_all = L.off[max_lvl] - L.off[0];
-      const bool one = all_lvls && n_all <= 65535;
-      const int n = one ? (lvl == 1 ? n_all : 0) : L.n(lvl);
       const bool mx = max_out && !part;
-      if (n) {
-        // columns of 8 on the large boxes: 693 against 728 us per 64^3 leaf
-        // launch (profiles/r03_ab_res_k.txt); small boxes keep their threads
-        const int rk = mg->res_k ? mg->res_k : nc >= 32 ? 8 : 4;
-        const int kc = nc % rk == 0 ? rk : nc % 4 == 0 ? 4 : 2;
-        const dim3 grid((n3 / kc + 255) / 256, n);
-        const bool gr = grad_fused(mg, max_lvl);
-        auto kern = gr ? (mx ? (kc == 8 ? k_residual<true, 8, true>
-                                        : kc == 4 ? k_residual<true, 4, true>
-                                                  : k_residual<true, 2, true>)
-                             : (kc == 8 ? k_residual<false, 8, true>
-                                        : kc == 4 ? k_residual<false, 4, true>
-                                                  : k_residual<false, 2, true>))
-                  : mx ? (kc == 8 ? k_residual<true, 8> : kc == 4 ? k_residual<true, 4>
-                                                                  : k_residual<true, 2>)
-                       : (kc == 8 ? k_residual<false, 8> : kc == 4 ? k_residual<false, 4>
-                                                                   : k_residual<false, 2>);
-        hipLaunchKernelGGL(kern, grid, dim3(256), 0, t->stream,
-                           t->ccv(mg->d.i_phi), t->ccv(mg->d.i_rhs),
-                           t->ccv(mg->d.i_tmp), L.at(lvl), nc, t->bsz, cf, red,
-                           one ? mg->d_lvl_c : nullptr, (one || gr) ? t->d_boxes : nullptr,
-                           gr ? t->ccv(mg->grad_iv) : nullptr, mg->grad_fac);
-        AFH_LAUNCH_CHECK("k_residual");
-      }
-      const int nv = mg->any_var ? Lv.n(lvl) : 0;
-      if (nv) {
-        hipLaunchKernelGGL(mx ? k_residual_v<true> : k_residual_v<false>,
-                           dim3((n3 + 255) / 256, nv), dim3(256), 0, t->stream,
-                           t->ccv(mg->d.i_phi), t->ccv(mg->d.i_rhs),
-                           t->ccv(mg->d.i_tmp), Lv.at(lvl), nc, t->bsz, mg->d_vp,
-                           mg->d_bp, red);
-        AFH_LAUNCH_CHECK("k_residual_v");
-      }
+      auto residual = [&](const LevelList &L, auto st) -> int32_t {
+        using St = decltype(st);
+        const int n_all = L.off[max_lvl] - L.off[0];
+        const bool one = !is_var<St> && all_lvls && n_all <= 65535;
+        const int n = one ? (lvl == 1 ? n_all : 0) : L.n(lvl);
+        if (!n) return AFH_OK;
+        double *phi = t->ccv(mg->d.i_phi), *rhs = t->ccv(mg->d.i_rhs), *tmp = t->ccv(mg->d.i_tmp);
+        with_bool(mx, [&](auto MX) {
+          if constexpr (is_var<St>)
+            hipLaunchKernelGGL(k_residual_v<decltype(MX)::value>, dim3((n3 + 255) / 256, n),
+                               dim3(256), 0, t->stream, phi, rhs, tmp, L.at(lvl), nc, t->bsz,
+                               st, red);
+          else
+            with_bool(gr, [&](auto GR) {
+              with_col(kc, [&](auto K) {
+                hipLaunchKernelGGL(
+                    (k_residual<decltype(MX)::value, decltype(K)::value, decltype(GR)::value>),
+                    dim3((n3 / K + 255) / 256, n), dim3(256), 0, t->stream, phi, rhs, tmp,
+                    L.at(lvl), nc, t->bsz, st.cf, red, one ? mg->d_lvl_c : nullptr,
+                    (one || GR) ? t->d_boxes : nullptr, GR ? t->ccv(mg->grad_iv) : nullptr,
+                    mg->grad_fac);
+              });
+            });
+        });
+        AFH_LAUNCH_CHECK(is_var<St> ? "k_residual_v" : "k_residual");
+        return AFH_OK;
+      };
+      const LevelList *all[] = {&t->ids, &t->leaves, &t->parents},
+                      *lc[] = {&mg->ids_c, &mg->leaves_c, &mg->parents_c},
+                      *lv[] = {&mg->ids_v, &mg->leaves_v, &mg->parents_v};
+      const int w = max_out ? 1 + part : 0;
+      if ((e = const_then_var(mg, lvl, *all[w], *lc[w], *lv[w], residual))) return e;
     }
   }
   if (!max_out) return AFH_OK;
@@ -4622,18 +4337,13 @@ int32_t afh_mg_compute_phi_gradient(afh_mg *mg, int32_t i_fc, double fac,
   const int ntot = t->ids.off[t->nlvl];
   double *nrm = i_norm > 0 ? t->ccv(i_norm) : nullptr;
   double *fcv = i_fc > 0 ? t->fcv(i_fc) : nullptr;
-  switch (nc) {
-  case 4: launch_gradient<4>(t, t->ccv(mg->d.i_phi), fcv, nrm, fac, mg->grad_nt); break;
-  case 8: launch_gradient<8>(t, t->ccv(mg->d.i_phi), fcv, nrm, fac, mg->grad_nt); break;
-  case 16: launch_gradient<16>(t, t->ccv(mg->d.i_phi), fcv, nrm, fac, mg->grad_nt); break;
-  case 32: launch_gradient<32>(t, t->ccv(mg->d.i_phi), fcv, nrm, fac, mg->grad_nt); break;
-  case 64: launch_gradient<64>(t, t->ccv(mg->d.i_phi), fcv, nrm, fac, mg->grad_nt); break;
-  default:
+  if (!with_nc(nc, [&](auto NC) {
+        launch_gradient<decltype(NC)::value>(t, t->ccv(mg->d.i_phi), fcv, nrm, fac, mg->grad_nt);
+      }))
     // every other box size: one thread per cell, any fcv / nrm combination
     hipLaunchKernelGGL(k_gradient, dim3((n3 + 255) / 256, ntot), dim3(256), 0,
                        t->stream, t->ccv(mg->d.i_phi), fcv, nrm, t->d_boxes,
                        t->ids.d, nc, t->bsz, t->fsz, fac);
-  }
   AFH_LAUNCH_CHECK("k_gradient");
   if (!mg->any_lsf) return AFH_OK;
   // electrode leaf boxes: mg_box_lpllsf_gradient, then their |E| again
@@ -4641,16 +4351,12 @@ int32_t afh_mg_compute_phi_gradient(afh_mg *mg, int32_t i_fc, double fac,
     const int n = mg->lsf_leaves.n(l);
     if (!n) continue;
     const double *dr = &t->lvl_dr[3 * (l - 1)];
-    auto par = [&](auto kern) {
-      hipLaunchKernelGGL(kern, dim3(n), dim3(256), 0, t->stream, t->ccv(mg->d.i_phi),
-                         t->ccv(mg->i_lsf), t->fcv(i_fc), mg->lsf_leaves.at(l), t->bsz,
-                         t->fsz, mg->d_lsf_n, mg->d_ix, mg->d_dd, mg->d_bv, fac / dr[0],
-                         fac / dr[1], fac / dr[2]);
-    };
-    if (nc == 4) par(k_lsf_gradient_par<4>);
-    else if (nc == 8) par(k_lsf_gradient_par<8>);
-    else if (nc == 16) par(k_lsf_gradient_par<16>);
-    else
+    if (!with_size<4, 8, 16>(nc, [&](auto NC) {
+          hipLaunchKernelGGL(k_lsf_gradient_par<decltype(NC)::value>, dim3(n), dim3(256), 0,
+                             t->stream, t->ccv(mg->d.i_phi), t->ccv(mg->i_lsf), t->fcv(i_fc),
+                             mg->lsf_leaves.at(l), t->bsz, t->fsz, mg->d_lsf_n, mg->d_ix,
+                             mg->d_dd, mg->d_bv, fac / dr[0], fac / dr[1], fac / dr[2]);
+        }))
       hipLaunchKernelGGL(k_lsf_gradient, dim3(n), dim3(64), 0, t->stream,
                          t->ccv(mg->d.i_phi), t->ccv(mg->i_lsf), t->fcv(i_fc),
                          mg->lsf_leaves.at(l), nc, t->bsz, t->fsz, mg->d_lsf_n,

@@ -34,8 +34,9 @@ def oracle():
 
 
 # smoother variants: "split" = one launch per half-sweep with the level ghost
-# fill in between (the reference's sequence); "fused" = k_gsrb_pair on every
-# level (AFH_GSRB_FUSED_MIN_BOXES=1), which must give the same bits
+# fill in between (the reference's sequence); "fused" = the fused pair
+# (k_gsrb_pair_box up to 16^3 boxes, k_gsrb_pair2 above) on every level
+# (AFH_GSRB_FUSED_MIN_BOXES=1), which must give the same bits
 # ("fused_tiles": the same with NC/4-row tiles per workgroup, the geometry of
 # levels with 64..255 boxes, AFH_GSRB_TILES=1)
 SMOOTHERS = {"split": ("0", "0"), "fused": ("1", "0"), "fused_tiles": ("1", "1")}
@@ -341,6 +342,35 @@ def test_electrode_bitwise_equals_oracle(hip, oracle, smoother, coarse):
     ra, rb = (golden.download(c, names[:3]) for c in cases)
     for n in names[:3]:
         assert np.array_equal(ra[n], rb[n]), n
+
+
+def test_electrode_residual_max_bitwise(hip, oracle):
+    """The leaf maximum of the residual folded into the residual pass on
+    electrode boxes (rod8: variable-stencil leaves, whose residual is rhs -
+    (L phi - bc_correction)): afh_mg_fas_vcycle_maxres returns the oracle's
+    V-cycle + af_tree_maxabs_cc(i_tmp) bitwise, which is also maxabs_cc of
+    its own tmp; phi and tmp equal the oracle's bitwise."""
+    g = golden.load("rod8")
+    var = {int(b) for b in g["lsf_v_ids"]}
+    leaves = {int(b) for l in range(1, int(g["highest_lvl"]) + 1)
+              for b in g["lvl_leaves_%d" % l]}
+    assert var & leaves and var - leaves  # folded (leaves) and plain (parents)
+    ca, cb = (golden.make_case(lib, g, coarse_cycles=12) for lib in (hip, oracle))
+    state = {**golden.stage_outputs(g, "init"), **golden.stage_outputs(g, "rhs")}
+    for c in (ca, cb):
+        golden.upload(c, state)
+    for _ in range(2):
+        ra = ca.mg.fas_vcycle_maxres()
+        cb.mg.fas_vcycle(True)
+        rb = cb.tree.maxabs_cc(IV["tmp"])
+        assert ra == rb and ra == ca.tree.maxabs_cc(IV["tmp"])
+        # the maximum lies on an electrode leaf (the oracle's tmp), so it is
+        # the variable-stencil kernel's fold that returned it
+        res = np.abs(cb.tree.get_cc(IV["tmp"])[:, 1:-1, 1:-1, 1:-1])
+        on = {v: max(res[b - 1].max() for b in ids)
+              for v, ids in (("var", var & leaves), ("const", leaves - var))}
+        assert ra == on["var"] and on["var"] > on["const"], on
+    _assert_same(ca, cb, [IV["phi"], IV["tmp"]])
 
 
 @pytest.mark.gpu
