@@ -85,6 +85,9 @@ struct afh_tree {
   std::vector<std::vector<int32_t>> h_ids, h_leaves, h_parents;
   // leaves next to a refinement boundary, per level (af_restrict_ref_boundary)
   afh::LevelList refb;
+  // boxes with a refinement boundary on an x face, per level: the fills
+  // without x faces (gc_lvl_var xfree) still fill theirs
+  afh::LevelList xrb;
   // (parent id, nb) tasks of af_consistent_fluxes, per level
   afh::LevelList cflux;
   // af_consistent_fluxes has a task anywhere in the whole topology (all
@@ -257,11 +260,16 @@ int32_t gc_lvl(afh_tree *t, int lvl, int iv, int corners, bool rims = false, int
 // depth: the replica layers the next reader of the level needs (2: a fused
 // pair follows -- it recomputes neighbours' boundary cells --, 1: only
 // ghost cells are read), handed to the hooks as their n
-// xrim: the x ghost cells facing same-level neighbours are current except
-// on rows 1, nc and planes 1, nc (k_gsrb_pair2<..., XR> stored them): only
-// those are filled
+// xfree: only k_gsrb_pair2 reads the fill (it fetches the x ghost cells
+// facing same-level neighbours and physical boundaries itself): the x faces
+// are left out, except on the boxes of t->xrb; ignored on a sharded tree
 int32_t gc_lvl_var(afh_tree *t, int lvl, int iv, const double *vc,
-                   const GcArgs &ga, int corners, bool rims = false, int depth = 2);
+                   const GcArgs &ga, int corners, bool rims = false, int depth = 2,
+                   bool xfree = false);
+// the boxes of ids[0..n) with a refinement boundary on an x face, appended
+// to out in list order (t->xrb; afh_xface_rb_boxes for the tests)
+void xface_rb_boxes(const afh_box_meta *boxes, const int32_t *ids, int n,
+                    std::vector<int32_t> &out);
 // edges and corners only of level lvl (k_gc_corners), for a level whose
 // faces a producer kernel filled (the fused pair's pushed faces)
 int32_t gc_lvl_corners(afh_tree *t, int lvl, int iv);

@@ -173,9 +173,25 @@ struct RbPar {
 //      physical / refinement faces use gc_face_nocopy with the box's current
 //      red and black values (coarse data from `coarse`, i.e. phi).
 //   C  black cells of plane s-1 (new red neighbours), in place in LDS
-//   D  plane s+2 (prefetched into registers during the step) -> LDS
+//   D  plane s+2 (prefetched into registers during the step) -> LDS; the B
+//      inputs of step s+1 (loaded at the top of the step by the TJ + NC
+//      lanes that own a B value) -> LDS (BL), where B of step s+1 reads them:
+//      no register holds them across a step
 //   E  plane s-2 of the tile, complete since step s-1, written once in full
 //      rows (with A)
+//   G  (with A) the black x ghost cells of plane s+1, which the pair fetches
+//      itself: one per row, loaded one step ahead by TJ + 2 lanes -- a
+//      same-level neighbour's boundary cell from `src` (periodic wrap and a
+//      box that is its own neighbour included), a physical face by
+//      gc_face_nocopy from the plane's own old values in LDS (k_gc_faces'
+//      call and values) -- over what the whole-row load brought. So a level
+//      fill that only this kernel reads may leave out the x faces
+//      (gc_lvl_var xfree) except: their rim (rows and planes 1, NC), which
+//      B and the z ghost planes read from memory through the y / z
+//      neighbours whose boundary cells they recompute, and the x faces at a
+//      refinement boundary, which are not fetched here. The halo rows of a
+//      tile take the adjacent tile's x ghost cells from LDS likewise. The
+//      fetch is unconditional: after a full fill it brings the same values.
 // Each plane of phi and rhs is read once and phi is written once per pair
 // (24 B/cell algorithmic).
 // Parity mapping: in step s thread t owns the same RPT (i, j) columns for
@@ -185,8 +201,12 @@ struct RbPar {
 // DEPTH: planes of phi / rhs in flight per workgroup (1: loaded and stored
 // in the same step; 2: loaded one step earlier). Plane rows are stored
 // whole, x ghost cells included (one contiguous run per tile plane, no
-// partially written cache lines; the level fill after the pair rewrites
-// every ghost cell of dst).
+// partially written cache lines): the stored x ghost cells are the fetched
+// old black values and B's red ones; the next reader fetches its own (this
+// kernel) or follows a full level fill.
+// Resources (profiles/pair_xfetch_kernel_resources.txt): <64, 64, 1, 1> runs
+// 1024 threads, so 128 VGPRs is its ceiling; with the B inputs in LDS the
+// fetch fits it without scratch.
 // KS: the k planes split into KS chunks, one workgroup each (levels with
 // too few boxes to fill the chip): a chunk recomputes the red cells of the
 // plane below it (as tiles recompute halo rows) and stores its own planes.
@@ -206,6 +226,7 @@ __global__ void __launch_bounds__((RbPar<NC, TJ>::NT))
                 EPT = G::EPT;
   constexpr size_t SK = (size_t)NG * NG;
   __shared__ double P[4][PL];  // planes s-2 .. s+1 at slot (plane & 3)
+  __shared__ double BL[7][TJ + NC];  // the B inputs of the next step
   // LDS row layout (split parity): each row holds its even-i cells, then
   // its odd-i cells, so the red (black) cells the lanes of a row update and
   // all their neighbours are unit-stride in LDS (no bank conflicts); the
@@ -279,7 +300,6 @@ __global__ void __launch_bounds__((RbPar<NC, TJ>::NT))
     rBn[q] = odd ? lo : hi;
     rB[q] = 0.0;
   }
-  __syncthreads();
 
   // B inputs (one step ahead, so phase B never waits on them): thread
   // u < TJ + NC owns one red ghost value of plane s. A same-level
@@ -376,7 +396,57 @@ __global__ void __launch_bounds__((RbPar<NC, TJ>::NT))
     }
     return b;
   };
-  BIn bc = load_b(s0);
+  // one step's B inputs wait in LDS (BL, written in D, read in the next
+  // step's B; the barrier after C separates the two): held in registers they
+  // cost 14 VGPRs in every wave for values two waves use
+  const BIn b0 = load_b(s0);
+  // The black x ghost cells, fetched by the pair itself (the level fill
+  // before it may leave out the x faces): thread u < TJ + 2 owns LDS row u of
+  // the plane in flight; of its two x ghost cells the black one is
+  // i = 0 (j + k even) or NC + 1. A same-level neighbour's boundary cell
+  // comes from its `src` (copy_from_nb), loaded one step ahead like the
+  // plane; a physical face is gc_face_nocopy on the plane's own old values in
+  // LDS (k_gc_faces' call). put_g overwrites what the whole-row load brought,
+  // a barrier after D. Refinement boundaries keep the fill's value. (The red
+  // x ghosts are B's.)
+  auto g_side = [&](int kp, int &j, int &nb) {
+    j = j0 - 1 + tid;
+    nb = ((j + kp) & 1) ? 2 : 1;
+    return tid < TJ + 2 && j >= 1 && j <= NC && kp >= 1 && kp <= NC;
+  };
+  auto load_g = [&](int kp) {
+    int j, nb;
+    const bool ok = g_side(kp, j, nb);
+    const int nb_id = nb == 1 ? nb1 : nb2;
+    const bool cp = ok && nb_id > 0;
+    const double *xs = cp ? src + (size_t)(nb_id - 1) * bsz : x;
+    return xs[cp ? ix3(NG, nb == 1 ? NC : 1, j, kp) : ix3(NG, 1, j0, 1)];
+  };
+  auto put_g = [&](int kp, double *Pk, double g) {
+    int j, nb;
+    if (!g_side(kp, j, nb)) return;
+    const int nb_id = nb == 1 ? nb1 : nb2;
+    const int gi = nb == 1 ? 0 : NC + 1;
+    if (nb_id > 0) {
+      Pk[L(tid, gi)] = g;
+    } else if (nb_id < 0) {
+      const int p[3] = {gi, j, kp};
+      Pk[L(tid, gi)] = gc_face_nocopy_k(coarse, meta, m, nb, nb_id, dr0, p, j, kp, NC, bsz,
+                                        bcof(nb), ga.rb,
+                                        [&](const int *q) { return Pk[L(tid, q[0])]; });
+    }
+  };
+  // (the first B inputs and ghost cells are in flight with the first planes:
+  // one memory latency before the first step, as without them)
+  const double g0 = load_g(s0);
+  double gx = load_g(s0 + 1);
+  __syncthreads();  // planes s0-1 .. s0+1 in LDS
+  if (tid < NBL) {
+#pragma unroll
+    for (int q = 0; q < 7; q++) BL[q][tid] = b0.bl[q];
+  }
+  put_g(s0, P[s0 & 3], g0);
+  __syncthreads();
   // phi planes and rhs rows in flight: loaded in step s, consumed (LDS /
   // rotation) in step s+1 -- two planes of each per workgroup in flight
   struct Pf {
@@ -417,9 +487,12 @@ __global__ void __launch_bounds__((RbPar<NC, TJ>::NT))
   // written between B and C (C reads it; it reads the black cells C
   // updates).
   auto step = [&](const int s, Pf &ld, const Pf &cn) {
+    // the black x ghosts of plane s+1 (in LDS since D of step s-1; first
+    // read by B of this step), then those of plane s+2 into flight
+    if (s + 1 <= k1 + 1) put_g(s + 1, P[(s + 1) & 3], gx);
+    gx = load_g(s + 2);
     const BIn bn = load_b(s + 1);
     load_pf(ld, s + 1 + DEPTH);
-    double *bl = bc.bl;
     const BDesc bd = bdesc(s);
     const int b_i = bd.i, b_j = bd.j, b_jl = bd.jl, b_nb = bd.nb, b_rep = bd.rep;
     const bool b_pre = bd.pre, b_lm = bd.lm, b_lp = bd.lp, b_zm = bd.zm, b_zp = bd.zp;
@@ -446,6 +519,9 @@ __global__ void __launch_bounds__((RbPar<NC, TJ>::NT))
     if (b_nb) {
       double v;
       if (b_pre) {
+        double bl[7];
+#pragma unroll
+        for (int q = 0; q < 7; q++) bl[q] = BL[q][tid];
         if (b_rep >= 0) {
           // x1v: this box's cell next to the face (black, old)
           const int d = b_rep >> 1;
@@ -455,6 +531,12 @@ __global__ void __launch_bounds__((RbPar<NC, TJ>::NT))
 #pragma unroll
           for (int q = 0; q < 6; q++)
             if (q == b_rep) bl[q] = x1v;
+        }
+        if constexpr (TJ < NC) {
+          // the adjacent tile's row: its x ghost cells are this box's, in
+          // LDS (put_g), not necessarily in memory
+          if (b_nb == 7 && b_i == 1) bl[0] = P0[L(b_jl, 0)];
+          if (b_nb == 7 && b_i == NC) bl[1] = P0[L(b_jl, NC + 1)];
         }
         if (b_lm) bl[2] = P0[L(b_jl - 1, b_i)];
         if (b_lp) bl[3] = P0[L(b_jl + 1, b_i)];
@@ -522,7 +604,10 @@ __global__ void __launch_bounds__((RbPar<NC, TJ>::NT))
       rR[q] = odd ? cn.nhi[q] : cn.nlo[q];
       rBn[q] = odd ? cn.nlo[q] : cn.nhi[q];
     }
-    bc = bn;
+    if (tid < NBL) {
+#pragma unroll
+      for (int q = 0; q < 7; q++) BL[q][tid] = bn.bl[q];
+    }
     __syncthreads();
   };
   if (DEPTH == 1) {
@@ -2606,7 +2691,8 @@ struct afh_mg {
   // their ghost cells filled by the previous (one level lower) V-cycle's up
   // leg or the level-1 solve, so the restriction may push faces there too
   bool in_fmg = false;
-  int tiles_min = 256;  // levels of fewer boxes run tiles (NC >= 32)
+  bool pair_xfetch = true;  // AFH_PAIR_XFETCH: fills only a fused pair reads skip the x faces
+  int tiles_min = 256;  // levels of fewer boxes run tiles (NC >= 32; AFH_GSRB_TILES_MIN)
   int *d_cycles = nullptr;
   int cycles_host = 0;
   bool cycles_on_dev = false;
@@ -2931,6 +3017,8 @@ int32_t afh_mg_create(afh_tree *t, const afh_mg_desc *d, afh_mg **out) {
     mg->prolong_k = atoi(env) == 8 ? 8 : atoi(env) == 2 ? 2 : 4;
   if (const char *env = getenv("AFH_CS_ELEC_DIRECT")) mg->csd_on = atoi(env) != 0;
   if (const char *env = getenv("AFH_CS_DIRECT_SMALL")) mg->cs_direct_small = atoi(env) != 0;
+  if (const char *env = getenv("AFH_GSRB_TILES_MIN")) mg->tiles_min = atoi(env);
+  if (const char *env = getenv("AFH_PAIR_XFETCH")) mg->pair_xfetch = atoi(env) != 0;
   if (const char *env = getenv("AFH_PAIR_PUSH")) mg->pair_push = atoi(env) != 0;
   if (const char *env = getenv("AFH_PROLONG_PUSH")) mg->prolong_push = atoi(env) != 0;
   if (const char *env = getenv("AFH_RSTR_PUSH")) mg->rstr_push = atoi(env) != 0;
@@ -3079,6 +3167,15 @@ static void launch_pair2(afh_mg *mg, int lvl, const double *src, double *dst,
 // through the exchange hooks) or AFH_PAIR_PUSH=0
 static bool pair_push(const afh_mg *mg) {
   return mg->pair_push && mg->t->nc <= 16 && !mg->t->hook;
+}
+
+// k_gsrb_pair2 fetches the x ghost cells of the box it smooths, so a level
+// fill that nothing but such a pair reads leaves out the x faces (gc_lvl_var
+// xfree): the fill between two pairs of a leg, and the fill after the
+// correction when the up leg starts with a pair. Not on a sharded tree (the
+// replicas' ghost protocol is untouched). AFH_PAIR_XFETCH=0: full fills.
+static bool pair_xfetch(const afh_mg *mg) {
+  return mg->pair_xfetch && mg->t->nc >= 32 && !mg->t->hook;
 }
 
 // pend: rhs round trips of earlier pairs of the leg not yet stored (read
@@ -3278,7 +3375,9 @@ static int32_t gsrb_boxes(afh_mg *mg, int lvl, bool up, bool stale_ghosts = fals
                                       // second layer: the leg's next pair, or
                                       // the next V-cycle's first on the
                                       // highest level (no fill between)
-                                      n < n_cycle || (up && lvl == mg->vc_max_lvl) ? 2 : 1)) {
+                                      n < n_cycle || (up && lvl == mg->vc_max_lvl) ? 2 : 1,
+                                      // only the leg's next pair reads it
+                                      n < n_cycle && pair_xfetch(mg))) {
       return e;
     }
   }
@@ -4123,7 +4222,11 @@ static int32_t vcycle_body(afh_mg *mg, int32_t set_residual, int max_lvl, bool m
     if (!prolong_push(mg, lvl) &&
         (e = gc_lvl_var(t, lvl, mg->d.i_phi, t->ccv(mg->d.i_phi),
                         t->gc_args(mg->d.i_phi), 1, fused_level(mg, lvl),
-                        fused_level(mg, lvl) ? 2 : 1)))
+                        fused_level(mg, lvl) ? 2 : 1,
+                        // the up leg starts with a fused pair (an odd count
+                        // starts with split half-sweeps, which read x ghosts)
+                        fused_level(mg, lvl) && pair_xfetch(mg) && mg->d.n_cycle_up >= 2 &&
+                            !(mg->d.n_cycle_up & 1))))
       return e;
     if ((e = gsrb_boxes(mg, lvl, true))) return e;
   }

@@ -75,22 +75,53 @@ void prof_end(afh_tree *t, int kc, double bytes) {
 }
 
 // ------------------------------------------------------------ faces
-// One thread per ghost cell of face (blockIdx.y+1) of box ids[blockIdx.z].
+// One thread per ghost cell of face (blockIdx.y+1) of box ids[blockIdx.z]
+// (6 block rows: every face; 2: the x faces).
+// xrim: of the x faces only the rim, rows 1, nc and planes 1, nc (4 nc
+// threads per face, the corner cells twice with the same value). The fused
+// pair k_gsrb_pair2 reads no other x ghost cell from memory: it fetches the
+// x ghost cells of the box it smooths itself, and recomputing a y or z
+// neighbour's boundary cell it reads that neighbour's x ghost cells on the
+// row or plane next to the box. The grid is then (gc_faces_xrim_blocks, 1,
+// boxes): the blocks of faces 3 .. 6, then those of the two rims (no block
+// row of mostly idle blocks for them).
 // Coarse data (refinement boundaries) are read from vc.
+__host__ __device__ inline int gc_faces_xrim_blocks(int nc) {
+  return 4 * ((nc * nc + 255) / 256) + (8 * nc + 255) / 256;
+}
 __global__ void k_gc_faces(double *__restrict__ v,
                            const double *__restrict__ vc,
                            const afh_box_meta *__restrict__ meta,
                            const int32_t *__restrict__ ids, int nc, size_t bsz,
-                           GcArgs ga) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= nc * nc) return;
+                           GcArgs ga, int xrim) {
+  int t = blockIdx.x * blockDim.x + threadIdx.x;
   const int id = ids[blockIdx.z];
-  const int nb = blockIdx.y + 1;
+  int nb = blockIdx.y + 1;
+  bool rim = false;
+  if (xrim) {
+    const int nblk = (nc * nc + 255) / 256, bx = blockIdx.x;
+    rim = bx >= 4 * nblk;
+    if (rim) {
+      t -= 4 * nblk * 256;
+      if (t >= 8 * nc) return;
+      nb = 1 + t / (4 * nc);
+      t %= 4 * nc;
+    } else {
+      nb = 3 + bx / nblk;
+      t -= (bx / nblk) * nblk * 256;
+    }
+  }
   const int d = (nb - 1) >> 1;
   const bool low = ((nb - 1) & 1) == 0;
   const int ta = (d == 0) ? 1 : 0, tb = (d == 2) ? 1 : 2;
   int a, b;
-  if ((nc & (nc - 1)) == 0) {
+  if (rim) {
+    const int side = t / nc, pos = t % nc + 1;
+    a = side == 0 ? 1 : side == 1 ? nc : pos;
+    b = side == 2 ? 1 : side == 3 ? nc : pos;
+  } else if (t >= nc * nc) {
+    return;
+  } else if ((nc & (nc - 1)) == 0) {
     a = (t & (nc - 1)) + 1;
     b = (t >> __builtin_ctz(nc)) + 1;
   } else {
@@ -310,8 +341,16 @@ int32_t call_hook(afh_tree *t, int kind, int lvl, int iv, double *vals, int n) {
   return AFH_OK;
 }
 
+void xface_rb_boxes(const afh_box_meta *boxes, const int32_t *ids, int n,
+                    std::vector<int32_t> &out) {
+  for (int q = 0; q < n; q++) {
+    const afh_box_meta &m = boxes[ids[q] - 1];
+    if (m.neighbors[0] == 0 || m.neighbors[1] == 0) out.push_back(ids[q]);
+  }
+}
+
 int32_t gc_lvl_var(afh_tree *t, int lvl, int iv, const double *vc,
-                   const GcArgs &ga, int corners, bool rims, int depth) {
+                   const GcArgs &ga, int corners, bool rims, int depth, bool xfree) {
   const int n = t->ids.n(lvl);
   double *v = t->var(iv);
   int32_t e;
@@ -334,10 +373,21 @@ int32_t gc_lvl_var(afh_tree *t, int lvl, int iv, const double *vc,
       prof_end(t, AFH_PROF_GHOST, 16.0 * 6 * nc * nc * n);
       AFH_LAUNCH_CHECK("k_gc_box");
     } else {
-      hipLaunchKernelGGL(k_gc_faces, dim3((nc * nc + 255) / 256, 6, n), dim3(256), 0,
-                         t->stream, v, vc, t->d_boxes, t->ids.at(lvl), nc, t->bsz, ga);
+      // xfree (never on a sharded tree: the replicas' ghost protocol is not
+      // the pair's): of the x faces only the rim, and in full on the boxes
+      // whose x ghost cells a fused pair cannot fetch (refinement boundaries)
+      const bool nox = xfree && !t->hook;
+      const int nx = nox ? t->xrb.n(lvl) : 0;
+      const dim3 grid = nox ? dim3(gc_faces_xrim_blocks(nc), 1, n)
+                            : dim3((nc * nc + 255) / 256, 6, n);
+      hipLaunchKernelGGL(k_gc_faces, grid, dim3(256), 0, t->stream, v, vc, t->d_boxes,
+                         t->ids.at(lvl), nc, t->bsz, ga, nox ? 1 : 0);
+      if (nx)
+        hipLaunchKernelGGL(k_gc_faces, dim3((nc * nc + 255) / 256, 2, nx), dim3(256), 0,
+                           t->stream, v, vc, t->d_boxes, t->xrb.at(lvl), nc, t->bsz, ga, 0);
       // algorithmic bytes: read one interior layer + write one ghost layer
-      prof_end(t, AFH_PROF_GHOST, 16.0 * 6 * nc * nc * n);
+      prof_end(t, AFH_PROF_GHOST,
+               16.0 * nc * ((nox ? 4.0 * nc + 8.0 : 6.0 * nc) * n + 2.0 * nc * nx));
       AFH_LAUNCH_CHECK("k_gc_faces");
       if (corners) {
         hipLaunchKernelGGL(k_gc_corners, dim3(n), dim3(fit_blk(12 * nc)), 0, t->stream, v,
@@ -865,8 +915,9 @@ static int32_t tree_create_impl(const afh_tree_desc *d, int32_t device,
     }
   }
   // derived task lists
-  std::vector<std::vector<int32_t>> refb(t->nlvl), cfl(t->nlvl);
+  std::vector<std::vector<int32_t>> refb(t->nlvl), cfl(t->nlvl), xrb(t->nlvl);
   for (int l = 0; l < t->nlvl; l++) {
+    xface_rb_boxes(t->boxes.data(), t->h_ids[l].data(), (int)t->h_ids[l].size(), xrb[l]);
     for (int32_t id : t->h_leaves[l]) {
       const afh_box_meta &m = t->boxes[id - 1];
       bool any = false;
@@ -886,7 +937,8 @@ static int32_t tree_create_impl(const afh_tree_desc *d, int32_t device,
   if ((e = upload_list(t, t->ids, t->h_ids)) ||
       (e = upload_list(t, t->leaves, t->h_leaves)) ||
       (e = upload_list(t, t->parents, t->h_parents)) ||
-      (e = upload_list(t, t->refb, refb)) || (e = upload_list(t, t->cflux, cfl)))
+      (e = upload_list(t, t->refb, refb)) || (e = upload_list(t, t->cflux, cfl)) ||
+      (e = upload_list(t, t->xrb, xrb)))
     return e;
   AFH_HIP(hipMalloc(&t->d_boxes, sizeof(afh_box_meta) * t->nb));
   AFH_HIP(hipMemcpy(t->d_boxes, t->boxes.data(), sizeof(afh_box_meta) * t->nb,
@@ -961,11 +1013,27 @@ int32_t afh_profile_read(afh_tree *t, double *total_ms, int64_t *launches,
   return AFH_OK;
 }
 
+// The boxes of level lvl of a topology whose x faces a fill without x faces
+// still fills (afh_tree::xrb), for the tests: host only, no device needed,
+// not part of the ABI of include/afivo_hip.h. *n: their number; the first
+// min(*n, cap) ids go to out.
+int32_t afh_xface_rb_boxes(const afh_tree_desc *d, int32_t lvl, int32_t *out, int32_t cap,
+                           int32_t *n) {
+  if (!d || !n || lvl < 1 || lvl > d->highest_lvl)
+    return set_error(AFH_ERR_ARG, "afh_xface_rb_boxes");
+  std::vector<int32_t> v;
+  xface_rb_boxes(d->boxes, d->lvl_ids + d->lvl_ids_off[lvl - 1],
+                 d->lvl_ids_off[lvl] - d->lvl_ids_off[lvl - 1], v);
+  *n = (int32_t)v.size();
+  for (int q = 0; q < *n && q < cap; q++) out[q] = v[q];
+  return AFH_OK;
+}
+
 int32_t afh_tree_destroy(afh_tree *t) {
   if (!t) return AFH_OK;
   hipStreamSynchronize(t->stream);
   for (hipEvent_t e : t->ev_pool) hipEventDestroy(e);
-  for (LevelList *L : {&t->ids, &t->leaves, &t->parents, &t->refb, &t->cflux})
+  for (LevelList *L : {&t->ids, &t->leaves, &t->parents, &t->refb, &t->cflux, &t->xrb})
     hipFree(L->d);
   for (auto &p : t->plans) {
     hipFree(p.d_reg);
@@ -1601,7 +1669,7 @@ int32_t afh_tree_regrid(afh_tree *o, const afh_tree_desc *d, afh_tree **out) {
     for (int iv : t->auto_vars) {
       hipLaunchKernelGGL(k_gc_faces, dim3((nc * nc + 255) / 256, 6, n), dim3(256), 0,
                          t->stream, t->ccv(iv), t->ccv(iv), t->d_boxes, d_list, nc,
-                         t->bsz, t->gc_args(iv));
+                         t->bsz, t->gc_args(iv), 0);
       AFH_LAUNCH_CHECK("k_gc_faces");
       hipLaunchKernelGGL(k_gc_corners, dim3(n), dim3(fit_blk(12 * nc)), 0, t->stream, t->ccv(iv),
                          t->d_boxes, d_list, nc, t->bsz);
