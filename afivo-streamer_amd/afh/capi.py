@@ -218,6 +218,12 @@ SIGNATURES_2D = {
     "tree_get_coord": (i32, [_VP, P_i32]),
 }
 COORD_XYZ, COORD_CYL = 1, 2
+# the source factor (include/afivo_hip_srcfac.h): both HIP libraries have it,
+# the oracle and the common ABI do not
+SIGNATURES_SRCFAC = {
+    "fluid_set_source_factor": (i32, [_VP, i32, C.POINTER(C.c_uint8), f64, i32]),
+}
+SRCFAC_NONE, SRCFAC_FLUX = 0, 1
 DIST_LOCAL, DIST_RCCL = 1, 2
 HOOK_HALO, HOOK_RIMS, HOOK_RESTRICT, HOOK_MAX, HOOK_MIN, HOOK_CFLUX = 1, 2, 3, 4, 5, 6
 HOOK_SUM = 7
@@ -291,7 +297,7 @@ _loaded = {}
 def hip_library():
     """The product library. Raises if it was not built -- no CPU fallback."""
     if "hip" not in _loaded:
-        _loaded["hip"] = Library(HIP_LIB, "afh_")
+        _loaded["hip"] = Library(HIP_LIB, "afh_", extra=SIGNATURES_SRCFAC)
     return _loaded["hip"]
 
 
@@ -300,7 +306,8 @@ def hip_library_2d():
     its own, SIGNATURES_2D). Raises if it was not built -- no CPU fallback."""
     if "hip2d" not in _loaded:
         only = [n[len("afh_"):] for n in header_symbols("afivo_hip_2d.h")]
-        _loaded["hip2d"] = Library(HIP_LIB_2D, "afh_", extra=SIGNATURES_2D, only=only)
+        _loaded["hip2d"] = Library(HIP_LIB_2D, "afh_",
+                                   extra=dict(SIGNATURES_2D, **SIGNATURES_SRCFAC), only=only)
     return _loaded["hip2d"]
 
 

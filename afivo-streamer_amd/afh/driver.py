@@ -272,8 +272,10 @@ class Simulation:
         self.td = c.lt("td")
         self.chem = c.lt("chem")
         self.reactions = []
+        self.ionization = []  # reaction_type == ionization_reaction (m_chemistry.f90:14)
         for n in range(1, n_reac + 1):
-            rt, _, n_coeff, lti, _ = c.ia("reaction_%d" % n)
+            rt, kind, n_coeff, lti, _ = c.ia("reaction_%d" % n)
+            self.ionization.append(kind == 1)
             if n_coeff > 4:
                 raise NotImplementedError("rate with %d coefficients" % n_coeff)
             # constant N: the gas species are folded into the rate factors
@@ -288,6 +290,30 @@ class Simulation:
                 "ix_in": shift(c.ia("reaction_%d_in" % n)),
                 "ix_out": shift(c.ia("reaction_%d_out" % n)),
                 "mult_out": c.ia("reaction_%d_mult" % n)})
+        # fixes%source_factor, fixes%source_min_electrons_per_cell and
+        # fixes%write_source_factor (m_streamer.f90:420-440): optional in the
+        # case dict, no factor when absent
+        self.source_factor = capi.SRCFAC_NONE
+        self.source_min_electrons = -1e100
+        self.i_srcfac = 0
+        if "source_factor" in c.d:
+            modes = {"none": capi.SRCFAC_NONE, "flux": capi.SRCFAC_FLUX}
+            if c.s("source_factor") not in modes:
+                raise ValueError("source_factor %r: options are none, flux"
+                                 % c.s("source_factor"))
+            self.source_factor = modes[c.s("source_factor")]
+        if "source_min_electrons_per_cell" in c.d:
+            self.source_min_electrons = c.r("source_min_electrons_per_cell")
+        if self.source_factor != capi.SRCFAC_NONE:
+            if not lib.has("fluid_set_source_factor"):
+                raise NotImplementedError(
+                    "source_factor = flux is not built in this library "
+                    "(include/afivo_hip_srcfac.h: the HIP libraries)")
+            if "write_source_factor" in c.d and c.i("write_source_factor"):
+                if "srcfac" not in self.cc_names:
+                    raise ValueError("write_source_factor: no cc variable named srcfac "
+                                     "in cc_names")
+                self.i_srcfac = self.cc_names.index("srcfac") + 1
         # init conditions (m_init_cond.f90:38-144)
         self.background = c.r("background_density")
         self.seeds = []
@@ -394,6 +420,10 @@ class Simulation:
                     "ion secondary emission (ion_se_yield > 0) is not built in this "
                     "library (the 2-D build: include/afivo_hip_2d.h)")
             self.fluid.set_ion_se_yield(c.r("ion_se_yield"))
+        # the source factor of add_source_terms (m_fluid.f90:368-397)
+        if self.source_factor != capi.SRCFAC_NONE:
+            self.fluid.set_source_factor(self.source_factor, self.ionization,
+                                         self.source_min_electrons, self.i_srcfac)
         if self.fused_rhs:
             self.fluid.set_rhs_output(self.i_rhs, True)
         self.faces_from_phi = self._faces_from_phi_ok and self.lsf is None

@@ -496,7 +496,7 @@ class Fluid:
             a.ix_out[:a.n_out] = r["ix_out"]
             a.mult_out[:a.n_out] = r["mult_out"]
         self._reactions = arr
-        d.n_reactions = len(reactions)
+        d.n_reactions = self.n_reactions = len(reactions)
         d.reactions = C.cast(arr, C.POINTER(capi.Reaction))
         d.dt_chemistry_nmin = dt_chemistry_nmin
         d.gas_temperature = gas_temperature
@@ -554,6 +554,24 @@ class Fluid:
         """input_data%ion_se_yield: forward_euler applies handle_ion_se_flux
         between the flux and the update (afh_fluid_set_ion_se_yield)."""
         self.lib.call("fluid_set_ion_se_yield", self.h, float(y))
+
+    def set_source_factor(self, mode, ionization=None, min_electrons=-1.0, i_srcfac=0):
+        """fixes%source_factor (afh_fluid_set_source_factor): with
+        capi.SRCFAC_FLUX the update scales the rates of the reactions flagged
+        in `ionization` (one flag per reaction) by |electron flux at the cell
+        centre| / (n_e mu |E|) clipped to [0, 1]; zero where n_e min(dr)**3 <
+        min_electrons (> 0); stored in cc variable i_srcfac (0: not stored).
+        capi.SRCFAC_NONE: off."""
+        flags = None
+        if ionization is not None:
+            if len(ionization) != self.n_reactions:
+                raise ValueError("set_source_factor: %d ionization flags for %d reactions"
+                                 % (len(ionization), self.n_reactions))
+            self._sf_flags = np.ascontiguousarray(
+                [1 if x else 0 for x in ionization], dtype=np.uint8)
+            flags = self._sf_flags.ctypes.data_as(C.POINTER(C.c_uint8))
+        self.lib.call("fluid_set_source_factor", self.h, int(mode), flags,
+                      float(min_electrons), int(i_srcfac))
 
     def ion_se_flux(self):
         """handle_ion_se_flux over the leaves (afh_fluid_ion_se_flux)."""

@@ -58,7 +58,11 @@
 // variable half-sweep (924-934), is a kernel of its own: every cell's rhs
 // makes the bc_correction round trip, one thread per cell. The fused pair is
 // k2_pair_box<NC, LPB, CYL, VAR>, the species update k2_update<NS, CYL, PHOTO,
-// MASK, IONS>.
+// MASK, IONS, SRCFAC>.
+//
+// The flux-based source factor (afh_fluid_set_source_factor, include/
+// afivo_hip_srcfac.h): SRCFAC of the update (compute_source_factor,
+// src/m_fluid.f90:525-583, and its use at 368-397).
 //
 // Cylindrical coordinates (af_cyl, afh_tree_set_coord): StCyl, CYL of the
 // pair and of the update (m_af_flux_schemes.f90:395-406), k2_consistent_cyl
@@ -100,6 +104,7 @@
 #include <vector>
 
 #include "../../include/afivo_hip_2d.h"
+#include "../../include/afivo_hip_srcfac.h"
 #include "afh_cs_tables.h"
 #include "afh_pfmg_dev.h"
 
@@ -1609,8 +1614,8 @@ __device__ __forceinline__ double rate_of(const UpdArgs &A, const DevReaction &R
 // species count when it is a compile-time case (the per-cell arrays then stay
 // in registers; wave-uniform indices use VGPR index mode), MAXS for any count
 // (A.ns; the arrays in scratch). One kernel, k2_update<NS, CYL, PHOTO, MASK,
-// IONS>; a feature that is off is compiled out and its argument block is
-// empty (UpdOpt).
+// IONS, SRCFAC>; a feature that is off is compiled out and its argument block
+// is empty (UpdOpt).
 //
 // CYL (a cylindrical tree): the r-fluxes times af_cyl_flux_factors inside the
 // divergence (m_af_flux_schemes.f90:395-406)
@@ -1647,6 +1652,32 @@ struct IonUpdArgs {
   const double *F[AFH_MAX_IONS];
 };
 
+// SRCFAC (afh_fluid_set_source_factor, fixes%source_factor = flux:
+// compute_source_factor and add_source_terms, src/m_fluid.f90:368-397,
+// 525-583): the rate coefficient of every reaction flagged in S.ion is
+// scaled by s = (fl + 1e-9) / (1e-9 + n_e mu |E|) clipped to [0, 1], fl =
+// 0.5 NORM2 of the electron flux summed over the cell's two faces per
+// dimension (no radius on a cylindrical tree), mu from the transport table at
+// the cell's field; s = 0 where n_e min(dr)**3 < S.min_e (> 0); s stored in
+// S.out (or null) on every cell of a box the mask leaves a cell of
+struct SrcFacArgs {
+  const uint8_t *ion;
+  double min_e;
+  double *out;
+  DevLT td;
+};
+
+// NORM2 of (a, b) as the Fortran runtime of the reference build evaluates it:
+// the largest magnitude m, the other over m squared; m sqrt(1 + s) -- not
+// sqrt(a a + b b), which differs in the last bit for about a third of all
+// inputs (afh.electrode.norm2 on the host)
+__device__ __forceinline__ double norm2_2(double a, double b) {
+  a = fabs(a), b = fabs(b);
+  if (a == 0.0) return b * sqrt(1 + 0.0);
+  const double t = b > a ? a / b : b / a;
+  return (b > a ? b : a) * sqrt(1 + t * t);
+}
+
 // f(std::true_type or std::false_type) for the run-time flag on
 template <class F> inline void with_flag(bool on, F &&f) {
   if (on) f(std::true_type{});
@@ -1661,17 +1692,19 @@ template <int N = 1, class F> inline void with_species_count(int ns, F &&f) {
   else with_species_count<N + 1>(ns, f);
 }
 
-template <bool PHOTO, bool MASK, bool IONS>
+template <bool PHOTO, bool MASK, bool IONS, bool SRCFAC = false>
 struct UpdOpt : ArgsIf<PHOTO, PhotoArgs, 0>, ArgsIf<MASK, MaskArgs, 1>,
-                ArgsIf<IONS, IonUpdArgs, 2> {};
+                ArgsIf<IONS, IonUpdArgs, 2>, ArgsIf<SRCFAC, SrcFacArgs, 3> {};
 
-template <int NS, bool CYL, bool PHOTO, bool MASK, bool IONS>
+template <int NS, bool CYL, bool PHOTO, bool MASK, bool IONS, bool SRCFAC = false>
 __global__ void __launch_bounds__(NT)
     k2_update(UpdArgs A, const int32_t *__restrict__ ids, const afh_box_meta *__restrict__ meta,
-              int nc, int bsz, int fsz, UpdOpt<PHOTO, MASK, IONS> O, unsigned long long *red) {
+              int nc, int bsz, int fsz, UpdOpt<PHOTO, MASK, IONS, SRCFAC> O,
+              unsigned long long *red) {
   const ArgsIf<PHOTO, PhotoArgs, 0> &P = O;
   const ArgsIf<MASK, MaskArgs, 1> &M = O;
   const ArgsIf<IONS, IonUpdArgs, 2> &I = O;
+  const ArgsIf<SRCFAC, SrcFacArgs, 3> &S = O;
   static_assert(!(CYL && MASK), "the update mask in cylindrical coordinates is not built");
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   double cmin = 1e100;
@@ -1693,10 +1726,31 @@ __global__ void __launch_bounds__(NT)
       dens[s] = v > 0.0 ? v : 0.0;
       der[s] = 0.0;
     }
-    const double field = 1e21 * A.inv_N * A.E[x];
+    const double ev = A.E[x];
+    const double field = 1e21 * A.inv_N * ev;
+    double sfac = 1.0;
+    if constexpr (SRCFAC) {
+      const double *Fe = A.F + (size_t)(id - 1) * fsz;
+      const int g0 = (j - 1) * nf + (i - 1), g2 = nf * nf;
+      const double mu = lt_col(S.td, 1, field) * A.inv_N;
+      const double ne = dens[A.e_index];
+      const double fl = 0.5 * norm2_2(Fe[g0] + Fe[g0 + 1], Fe[g2 + g0] + Fe[g2 + g0 + nf]);
+      sfac = (fl + 1e-9) / (1e-9 + ne * mu * ev);
+      sfac = fmin(1.0, sfac);
+      sfac = fmax(0.0, sfac);
+      if (S.min_e > 0) {
+        const double m = fmin(meta[id - 1].dr[0], meta[id - 1].dr[1]);
+        if (ne * (m * m * m) < S.min_e) sfac = 0.0;
+      }
+      // (add_source_terms returns before this for a wholly masked box)
+      if (S.out && src) S.out[x] = sfac;
+    }
     for (int r = 0; r < A.nr; r++) {
       const DevReaction &R = A.reac[r];
       double rate = rate_of(A, R, field);
+      if constexpr (SRCFAC) {
+        if (S.ion[r]) rate = rate * sfac;
+      }
       double prod = 1.0;
       for (int q = 0; q < R.n_in; q++) prod = prod * dens[R.ix_in[q] - 1];
       rate = rate * prod;
@@ -2062,6 +2116,12 @@ struct afh_fluid {
   // and each ion's 0-based species slot
   double *d_gc2 = nullptr;
   int e_index = -1;
+  // afh_fluid_set_source_factor: mode (AFH_SRCFAC_*), the per-reaction
+  // ionization flags on the device, the electron threshold and the cc
+  // variable the factor is stored in (0: not stored)
+  int sf_mode = 0, sf_iv = 0;
+  double sf_min_e = 0.0;
+  uint8_t *d_sf_ion = nullptr;
 };
 
 namespace afh2 {
@@ -3370,7 +3430,7 @@ int32_t afh_fluid_destroy(afh_fluid *f) {
   if (!f) return AFH_OK;
   hipStreamSynchronize(f->t->stream);
   hipFree(f->d_td), hipFree(f->d_chem), hipFree(f->d_reac);
-  hipFree(f->d_ids), hipFree(f->d_mstat), hipFree(f->d_gc2);
+  hipFree(f->d_ids), hipFree(f->d_mstat), hipFree(f->d_gc2), hipFree(f->d_sf_ion);
   delete f;
   return AFH_OK;
 }
@@ -3588,6 +3648,18 @@ static int32_t update(afh_fluid *f, double dt, int32_t s_deriv, int32_t n_prev,
     A.out[s] = t->ccv(iv + s_out);
   }
   if (A.e_index < 0) return set_error(AFH_ERR_ARG, "flux species is no species");
+  if (f->sf_mode != AFH_SRCFAC_NONE && f->sf_iv > 0) {
+    // the stored source factor may not be a variable this step reads or writes
+    bool used = f->sf_iv == f->mask_iv;
+    for (int s = 0; s < A.ns; s++) {
+      const int iv = f->d.species_iv[s];
+      used = used || f->sf_iv == iv + s_deriv || f->sf_iv == iv + s_out;
+      for (int q = 0; q < n_prev; q++) used = used || f->sf_iv == iv + s_prev[q];
+    }
+    if (used)
+      return set_error(AFH_ERR_ARG, "source factor: i_srcfac %d is a variable the step uses",
+                       f->sf_iv);
+  }
   for (int q = 0; q < n_prev; q++) A.w_prev[q] = w_prev[q];
   A.E = t->ccv(f->d.i_efld), A.F = t->fcv(f->d.f_flux), A.reac = f->d_reac;
   A.chem = dev_lt(f->d.chem, f->d_chem);
@@ -3626,20 +3698,27 @@ static int32_t update(afh_fluid *f, double dt, int32_t s_deriv, int32_t n_prev,
       I.s[q] = q < I.n ? f->d.ion_species[q] - 1 : 0;
       I.F[q] = q < I.n ? t->fcv(f->d.f_ion_flux[q]) : nullptr;
     }
+    const bool srcfac = f->sf_mode == AFH_SRCFAC_FLUX;
+    const SrcFacArgs S{f->d_sf_ion, f->sf_min_e, f->sf_iv > 0 ? t->ccv(f->sf_iv) : nullptr,
+                       dev_lt(f->d.td, f->d_td)};
     // one instantiation per combination of Cartesian / cylindrical / masked
-    // (the mask excludes cyl, above), photo and ions
+    // (the mask excludes cyl, above), photo, ions and the source factor
     with_species_count(A.ns, [&](auto ns) {
       auto kind = [&](auto cyl_, auto mask_) {
         with_flag(photo, [&](auto photo_) {
           with_flag(ions, [&](auto ions_) {
-            constexpr bool C = decltype(cyl_)::value, PH = decltype(photo_)::value,
-                           MK = decltype(mask_)::value, IO = decltype(ions_)::value;
-            UpdOpt<PH, MK, IO> O;
-            if constexpr (PH) static_cast<PhotoArgs &>(O) = P;
-            if constexpr (MK) static_cast<MaskArgs &>(O) = M;
-            if constexpr (IO) static_cast<IonUpdArgs &>(O) = I;
-            hipLaunchKernelGGL((k2_update<decltype(ns)::value, C, PH, MK, IO>), g, bk, 0,
-                               t->stream, A, ids, t->d_boxes, t->nc, t->bsz, t->fsz, O, red);
+            with_flag(srcfac, [&](auto srcfac_) {
+              constexpr bool C = decltype(cyl_)::value, PH = decltype(photo_)::value,
+                             MK = decltype(mask_)::value, IO = decltype(ions_)::value,
+                             SF = decltype(srcfac_)::value;
+              UpdOpt<PH, MK, IO, SF> O;
+              if constexpr (PH) static_cast<PhotoArgs &>(O) = P;
+              if constexpr (MK) static_cast<MaskArgs &>(O) = M;
+              if constexpr (IO) static_cast<IonUpdArgs &>(O) = I;
+              if constexpr (SF) static_cast<SrcFacArgs &>(O) = S;
+              hipLaunchKernelGGL((k2_update<decltype(ns)::value, C, PH, MK, IO, SF>), g, bk, 0,
+                                 t->stream, A, ids, t->d_boxes, t->nc, t->bsz, t->fsz, O, red);
+            });
           });
         });
       };
@@ -3707,6 +3786,43 @@ int32_t afh_fluid_set_update_mask(afh_fluid *f, int32_t i_lsf) {
   if (!f) return set_error(AFH_ERR_ARG, "afh_fluid_set_update_mask: null");
   if (i_lsf < 0 || i_lsf > f->t->nvc) return set_error(AFH_ERR_ARG, "bad i_lsf");
   f->mask_iv = i_lsf;
+  return AFH_OK;
+}
+
+int32_t afh_fluid_set_source_factor(afh_fluid *f, int32_t mode, const uint8_t *ionization,
+                                    double min_electrons_per_cell, int32_t i_srcfac) {
+  if (!f) return set_error(AFH_ERR_ARG, "afh_fluid_set_source_factor: null");
+  afh_tree *t = f->t;
+  if (mode != AFH_SRCFAC_NONE && mode != AFH_SRCFAC_FLUX)
+    return set_error(AFH_ERR_ARG, "afh_fluid_set_source_factor: unknown mode %d", mode);
+  if (mode == AFH_SRCFAC_FLUX && !ionization)
+    return set_error(AFH_ERR_ARG, "afh_fluid_set_source_factor: no ionization flags");
+  if (i_srcfac < 0 || i_srcfac > t->nvc)
+    return set_error(AFH_ERR_ARG, "afh_fluid_set_source_factor: bad i_srcfac %d", i_srcfac);
+  // (the other states of the species: update(), with the states of the step)
+  bool used = i_srcfac > 0 && (i_srcfac == f->d.i_efld || i_srcfac == f->d.i_photo ||
+                               i_srcfac == f->d.i_gas_dens || i_srcfac == f->mask_iv);
+  for (int s = 0; s < f->d.n_species && i_srcfac > 0; s++)
+    used = used || i_srcfac == f->d.species_iv[s];
+  if (used)
+    return set_error(AFH_ERR_ARG,
+                     "afh_fluid_set_source_factor: i_srcfac %d is a variable the step uses",
+                     i_srcfac);
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  H2(hipStreamIsCapturing(t->stream, &cs));
+  if (cs != hipStreamCaptureStatusNone)
+    return set_error(AFH_ERR_STATE, "afh_fluid_set_source_factor during a graph capture");
+  if (mode == AFH_SRCFAC_FLUX && f->d.n_reactions > 0) {
+    // (a queued update may still read the previous flags)
+    H2(hipStreamSynchronize(t->stream));
+    if (!f->d_sf_ion) H2(hipMalloc(&f->d_sf_ion, (size_t)f->d.n_reactions));
+    std::vector<uint8_t> flags(f->d.n_reactions);
+    for (int r = 0; r < f->d.n_reactions; r++) flags[r] = ionization[r] ? 1 : 0;
+    H2(hipMemcpy(f->d_sf_ion, flags.data(), flags.size(), hipMemcpyHostToDevice));
+  }
+  f->sf_mode = mode;
+  f->sf_min_e = min_electrons_per_cell;
+  f->sf_iv = i_srcfac;
   return AFH_OK;
 }
 

@@ -14,13 +14,16 @@
 //   k_consistent    af_consistent_fluxes (m_af_core.f90:1257-1402)
 //   k_update        flux_update_densities + add_source_terms + get_rates +
 //                   get_derivatives (m_af_flux_schemes.f90:320-436,
-//                   src/m_fluid.f90:298-466, src/m_chemistry.f90:565-688)
+//                   src/m_fluid.f90:298-466, src/m_chemistry.f90:565-688);
+//                   its SF instantiations with compute_source_factor
+//                   (src/m_fluid.f90:525-583, afh_fluid_set_source_factor)
 #include <algorithm>
 #include <type_traits>
 #include <utility>
 
 #include "afh_internal.h"
 #include "afh_networks.h"
+#include "../../include/afivo_hip_srcfac.h"
 
 namespace afh {
 
@@ -668,6 +671,47 @@ struct UpdArgs {
   const uint8_t *mstat;
 };
 
+// The flux-based source factor (afh_fluid_set_source_factor, fixes%
+// source_factor = flux: compute_source_factor and add_source_terms,
+// src/m_fluid.f90:368-397, 525-583): only the k_update<..., SF = true>
+// instantiations take these arguments, the others take UpdArgs as it is.
+struct SrcFacArgs {
+  const uint8_t *ion;  // per reaction: an ionization_reaction, its rate is scaled
+  double min_e;        // source_min_electrons_per_cell (<= 0: off)
+  double *out;         // the i_srcfac variable, or null
+  double dr3;          // minval(dr)**3 of this level (without UpdArgs::meta)
+};
+struct UpdArgsSf : UpdArgs {
+  SrcFacArgs sf;
+};
+
+// NORM2 of (a, b, c) as the Fortran runtime of the reference build evaluates
+// it (element by element: the largest magnitude m so far, s = the sum of
+// (x / m)^2 over the others, rescaled when m grows; m sqrt(1 + s)) -- not
+// sqrt(a a + b b + c c), which differs in the last bit for about a third of
+// all inputs. afh.electrode.norm2 is the same evaluation on the host.
+__device__ __forceinline__ void norm2_acc(double x, double &m, double &s) {
+  const double a = fabs(x);
+  if (m == 0.0) {
+    m = a;
+  } else if (a > m) {
+    const double t = m / a, tsq = t * t;
+    s = s * tsq;
+    s = s + tsq;
+    m = a;
+  } else {
+    const double t = a / m;
+    s = s + t * t;
+  }
+}
+__device__ __forceinline__ double norm2_3(double a, double b, double c) {
+  double m = 0.0, s = 0.0;
+  norm2_acc(a, m, s);
+  norm2_acc(b, m, s);
+  norm2_acc(c, m, s);
+  return m * sqrt(1 + s);
+}
+
 // Register-resident species arrays indexed by runtime reaction data (the
 // index is wave-uniform): direct indexing (VGPR index mode,
 // s_set_gpr_idx_on), or with AFH_UPD_SELECT=1 a select over every species.
@@ -1247,11 +1291,14 @@ __global__ void k_consistent(double *__restrict__ F,
 #ifndef AFH_UPD_MINW  // minimum waves per SIMD of the update kernel
 #define AFH_UPD_MINW 1
 #endif
+// SF: the source factor (SrcFacArgs) scales the flagged reactions' rates;
+// with the generic reaction loop only (launch_update)
 template <int NS, bool SLOW, int NP = MAXPREV, bool SD = true, bool GAS = false,
-          class NET = void>
+          class NET = void, bool SF = false>
 __global__ void __launch_bounds__(256, AFH_UPD_MINW)
-    k_update(UpdArgs A, const int32_t *__restrict__ ids, int nc, size_t bsz,
-             size_t fsz, unsigned long long *red) {
+    k_update(std::conditional_t<SF, UpdArgsSf, UpdArgs> A, const int32_t *__restrict__ ids,
+             int nc, size_t bsz, size_t fsz, unsigned long long *red) {
+  static_assert(!SF || std::is_void<NET>::value, "the source factor takes the generic loop");
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   const int id = ids[blockIdx.y];
   double cmin = 1e100, rmax = 0.0;
@@ -1323,6 +1370,29 @@ __global__ void __launch_bounds__(256, AFH_UPD_MINW)
     int clow = -1;
     double clf = 0.0;
     if (A.chem.rm) lt_loc(A.chem, field, clow, clf);
+    double sfac = 1.0;
+    if constexpr (SF) {
+      // compute_source_factor: |flux at the cell centre| / (n_e mu |E|),
+      // clipped to [0, 1]; mu from the transport table at the cell's field
+      const double ninv = GAS ? 1 / A.Ng[x] : A.inv_N;
+      const double mu = lt_col(A.td, 1, field) * ninv;
+      const double ne = sel(dens, A.e_index);
+      const double fl = 0.5 * norm2_3(fx0 + fx1, fy0 + fy1, fz0 + fz1);
+      sfac = (fl + 1e-9) / (1e-9 + ne * mu * ev);
+      sfac = fmin(1.0, sfac);
+      sfac = fmax(0.0, sfac);
+      if (A.sf.min_e > 0) {
+        double dr3 = A.sf.dr3;
+        if (A.meta) {
+          const double *dr = A.meta[id - 1].dr;
+          const double m = fmin(fmin(dr[0], dr[1]), dr[2]);
+          dr3 = m * m * m;
+        }
+        if (ne * dr3 < A.sf.min_e) sfac = 0.0;
+      }
+      // (add_source_terms returns before this for a wholly masked box)
+      if (A.sf.out && src) A.sf.out[x] = sfac;
+    }
     if constexpr (!std::is_void<NET>::value) {
       net_all<NET, SLOW>(A, field, Te, clow, clf, dens, der,
                          std::make_index_sequence<NET::NR>{});
@@ -1330,6 +1400,9 @@ __global__ void __launch_bounds__(256, AFH_UPD_MINW)
       for (int r = 0; r < A.nr; r++) {
         const DevReaction &R = A.reac[r];
         double rate = rate_of<SLOW>(A, R, field, Te, clow, clf);
+        if constexpr (SF) {
+          if (A.sf.ion[r]) rate = rate * sfac;
+        }
         double prod = 1.0;
         for (int q = 0; q < R.n_in; q++) prod = prod * sel(dens, R.ix_in[q] - 1);
         rate = rate * prod;
@@ -1439,12 +1512,30 @@ static bool launch_update_net(const UpdArgs &A, afh_tree *t, const dim3 &grid,
 
 template <int NS>
 void launch_update(const UpdArgs &A, afh_tree *t, int l, int n_boxes,
-                   unsigned long long *red, bool slow, int net = 0) {
+                   unsigned long long *red, bool slow, int net = 0,
+                   const SrcFacArgs *sf = nullptr) {
   // boxes leaves.at(l) .. + n_boxes (one level, or every level from 1)
   const int nc = t->nc, n3 = nc * nc * nc;
   const dim3 grid((n3 / AFH_UPD_KC + 255) / 256, n_boxes);
   const auto *ids = t->leaves.at(l);
   const bool sd = A.der_q < 0;
+  if (sf) {
+    // the source factor: the generic reaction loop with the per-reaction
+    // flags read at run time (no compiled network), any previous states
+    UpdArgsSf B;
+    static_cast<UpdArgs &>(B) = A;
+    B.sf = *sf;
+    if (A.Ng)
+      hipLaunchKernelGGL((k_update<NS, true, MAXPREV, true, true, void, true>), grid, dim3(256),
+                         0, t->stream, B, ids, nc, t->bsz, t->fsz, red);
+    else if (slow)
+      hipLaunchKernelGGL((k_update<NS, true, MAXPREV, true, false, void, true>), grid,
+                         dim3(256), 0, t->stream, B, ids, nc, t->bsz, t->fsz, red);
+    else
+      hipLaunchKernelGGL((k_update<NS, false, MAXPREV, true, false, void, true>), grid,
+                         dim3(256), 0, t->stream, B, ids, nc, t->bsz, t->fsz, red);
+    return;
+  }
   switch (net) {
 #define AFH_NET_CASE(K, NET) \
   case K:                   \
@@ -2100,6 +2191,12 @@ struct afh_fluid {
   int phi_iv = 0;
   double phi_fac = -1.0;
   double ion_se_yield = 0.0;  // afh_fluid_set_ion_se_yield
+  // afh_fluid_set_source_factor: mode (AFH_SRCFAC_*), the per-reaction
+  // ionization flags on the device, the electron threshold and the cc
+  // variable the factor is stored in (0: not stored)
+  int sf_mode = 0, sf_iv = 0;
+  double sf_min_e = 0.0;
+  uint8_t *d_sf_ion = nullptr;
   // mobile ions: second ghost layers of each ion [ion][box][6][nc][nc] and
   // the electrons' mu u per face (k_flux_staged -> k_flux_ion)
   double *d_gc2_ion = nullptr, *d_sig = nullptr;
@@ -2265,6 +2362,7 @@ int32_t afh_fluid_destroy(afh_fluid *f) {
   hipFree(f->d_gc2_ion);
   hipFree(f->d_sig);
   hipFree(f->d_mstat);
+  hipFree(f->d_sf_ion);
   delete f;
   return AFH_OK;
 }
@@ -2313,6 +2411,45 @@ int32_t afh_fluid_set_update_mask(afh_fluid *f, int32_t i_lsf) {
   AFH_LIVE(f->t, "afh_fluid_set_update_mask");
   if (i_lsf < 0 || i_lsf > f->t->nvc) return set_error(AFH_ERR_ARG, "bad i_lsf");
   f->mask_iv = i_lsf;
+  return AFH_OK;
+}
+
+int32_t afh_fluid_set_source_factor(afh_fluid *f, int32_t mode, const uint8_t *ionization,
+                                    double min_electrons_per_cell, int32_t i_srcfac) {
+  if (!f) return set_error(AFH_ERR_ARG, "afh_fluid_set_source_factor: null");
+  afh_tree *t = f->t;
+  AFH_LIVE(t, "afh_fluid_set_source_factor");
+  if (mode != AFH_SRCFAC_NONE && mode != AFH_SRCFAC_FLUX)
+    return set_error(AFH_ERR_ARG, "afh_fluid_set_source_factor: unknown mode %d", mode);
+  if (mode == AFH_SRCFAC_FLUX && !ionization)
+    return set_error(AFH_ERR_ARG, "afh_fluid_set_source_factor: no ionization flags");
+  if (i_srcfac < 0 || i_srcfac > t->nvc)
+    return set_error(AFH_ERR_ARG, "afh_fluid_set_source_factor: bad i_srcfac %d", i_srcfac);
+  // (the other states of the species: upd_args, with the states of the step)
+  bool used = i_srcfac > 0 && (i_srcfac == f->d.i_efld || i_srcfac == f->d.i_photo ||
+                               i_srcfac == f->d.i_gas_dens || i_srcfac == f->mask_iv ||
+                               i_srcfac == f->rhs_iv);
+  for (int s = 0; s < f->d.n_species && i_srcfac > 0; s++)
+    used = used || i_srcfac == f->d.species_iv[s];
+  if (used)
+    return set_error(AFH_ERR_ARG,
+                     "afh_fluid_set_source_factor: i_srcfac %d is a variable the step uses",
+                     i_srcfac);
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  AFH_HIP(hipStreamIsCapturing(t->stream, &cs));
+  if (cs != hipStreamCaptureStatusNone)
+    return set_error(AFH_ERR_STATE, "afh_fluid_set_source_factor during a graph capture");
+  if (mode == AFH_SRCFAC_FLUX && f->d.n_reactions > 0) {
+    // (a queued update may still read the previous flags)
+    AFH_HIP(hipStreamSynchronize(t->stream));
+    if (!f->d_sf_ion) AFH_HIP(hipMalloc(&f->d_sf_ion, AFH_MAX_REACTIONS));
+    uint8_t flags[AFH_MAX_REACTIONS];
+    for (int r = 0; r < f->d.n_reactions; r++) flags[r] = ionization[r] ? 1 : 0;
+    AFH_HIP(hipMemcpy(f->d_sf_ion, flags, f->d.n_reactions, hipMemcpyHostToDevice));
+  }
+  f->sf_mode = mode;
+  f->sf_min_e = min_electrons_per_cell;
+  f->sf_iv = i_srcfac;
   return AFH_OK;
 }
 
@@ -2507,6 +2644,18 @@ static int32_t upd_args(afh_fluid *f, double dt, int32_t s_deriv, int32_t n_prev
   for (int q = 0; q < n_prev; q++)
     if (bad(s_prev[q])) return set_error(AFH_ERR_ARG, "bad previous state");
   if (bad(s_deriv) || bad(s_out)) return set_error(AFH_ERR_ARG, "bad s_deriv / s_out");
+  if (f->sf_mode != AFH_SRCFAC_NONE && f->sf_iv > 0) {
+    // the stored source factor may not be a variable this step reads or writes
+    bool used = f->sf_iv == f->mask_iv || f->sf_iv == f->rhs_iv;
+    for (int s = 0; s < f->d.n_species; s++) {
+      const int iv = f->d.species_iv[s];
+      used = used || f->sf_iv == iv + s_deriv || f->sf_iv == iv + s_out;
+      for (int q = 0; q < n_prev; q++) used = used || f->sf_iv == iv + s_prev[q];
+    }
+    if (used)
+      return set_error(AFH_ERR_ARG, "source factor: i_srcfac %d is a variable the step uses",
+                       f->sf_iv);
+  }
   A.ns = f->d.n_species;
   A.nr = f->d.n_reactions;
   A.n_prev = n_prev;
@@ -2803,9 +2952,21 @@ static int32_t update_dev(afh_fluid *f, double dt, int32_t s_deriv, int32_t n_pr
     const int n = all_lvls ? (l == 1 ? t->leaves.off[t->nlvl] : 0) : t->leaves.n(l);
     if (!n) continue;
     for (int q = 0; q < 3; q++) A.dt_dr[q] = dt / t->lvl_dr[3 * (l - 1) + q];
+    SrcFacArgs S;
+    const bool sf_on = f->sf_mode == AFH_SRCFAC_FLUX;
+    if (sf_on) {
+      const double *dr = &t->lvl_dr[3 * (l - 1)];
+      const double m = std::min(std::min(dr[0], dr[1]), dr[2]);
+      S.ion = f->d_sf_ion;
+      S.min_e = f->sf_min_e;
+      S.out = f->sf_iv > 0 ? t->ccv(f->sf_iv) : nullptr;
+      S.dr3 = m * m * m;
+    }
+    const SrcFacArgs *sf = sf_on ? &S : nullptr;
     prof_begin(t, AFH_PROF_UPDATE);
     switch (A.ns) {
-#define AFH_CASE(N) case N: launch_update<N>(A, t, l, n, red, f->slow_rates, f->net); break;
+#define AFH_CASE(N) \
+  case N: launch_update<N>(A, t, l, n, red, f->slow_rates, f->net, sf); break;
       AFH_CASE(1) AFH_CASE(2) AFH_CASE(3) AFH_CASE(4) AFH_CASE(5) AFH_CASE(6)
       AFH_CASE(7) AFH_CASE(8) AFH_CASE(9) AFH_CASE(10) AFH_CASE(11)
       AFH_CASE(12) AFH_CASE(13) AFH_CASE(14) AFH_CASE(15) AFH_CASE(16)
@@ -2828,6 +2989,7 @@ static int32_t update_dev(afh_fluid *f, double dt, int32_t s_deriv, int32_t n_pr
     }
   }
   f->touch_state(s_out);
+  if (f->sf_mode == AFH_SRCFAC_FLUX && f->sf_iv > 0) t->touch(f->sf_iv);
   if (A.rhs) {
     t->touch(f->rhs_iv);
     f->rhs_state = s_out;
@@ -2983,7 +3145,8 @@ static int32_t fe_dev(afh_fluid *f, double dt, int32_t s_deriv, int32_t n_prev,
                      (nc == 16 || nc == 32 || nc == 64) && !t->any_cflux &&
                      !f->slow_rates && net_ok && f->d.i_gas_dens <= 0 &&
                      f->d.i_photo <= 0 && n_prev <= 2 && !alias &&
-                     f->d.limiter == AFH_LIM_KOREN && f->d.n_ions == 0 && !f->mask_iv;
+                     f->d.limiter == AFH_LIM_KOREN && f->d.n_ions == 0 && !f->mask_iv &&
+                     f->sf_mode == AFH_SRCFAC_NONE;  // (k_fe_lds has no source factor)
   if (!fused) {
     // flux and update back to back on the stream (the flux maxima are not
     // needed before the update); secondary emission from ions at the walls

@@ -525,6 +525,10 @@ int32_t afh_flux_upwind_tree(afh_fluid *f, int32_t s_deriv, double *dt_lim);
  * other cell adds no chemistry time-step limit (add_source_terms returns
  * before it, m_fluid.f90:332). i_lsf = 0: no mask (the default). */
 int32_t afh_fluid_set_update_mask(afh_fluid *f, int32_t i_lsf);
+/* The flux-based source factor of add_source_terms (fixes%source_factor =
+ * flux, m_fluid.f90:368-397 and 525-583) is built too; its entry point lies
+ * outside this common ABI (the C oracle does not have it) and is declared in
+ * afivo_hip_srcfac.h. */
 /* flux_update_densities with add_source_terms / set_box_mask
  * (m_af_flux_schemes.f90:320-436, src/m_fluid.f90:298-515); dt_lim[2] =
  * (chemistry limit on the last step, 1e100 otherwise; energy limit). */

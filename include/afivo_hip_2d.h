@@ -44,7 +44,10 @@
  * and refine_electrode_dx; below), and mobile ions (afh_fluid_desc.n_ions,
  * Cartesian and cylindrical: the fluxes of every flux species with the
  * per-face conductivity sum, their consistent fluxes and their divergences
- * in the update). Not built in 2-D
+ * in the update), and the flux-based source factor of the species update
+ * (fixes%source_factor = flux; its entry point is declared in
+ * afivo_hip_srcfac.h, outside the common ABI, and combines with cylindrical
+ * coordinates, photoionization, the update mask and mobile ions). Not built in 2-D
  * (AFH_ERR_UNSUPPORTED or not exported): electrodes in cylindrical
  * coordinates, variable
  * gas density, the temperature rate forms, sharding, ion
