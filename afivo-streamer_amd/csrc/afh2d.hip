@@ -3485,8 +3485,26 @@ static void flux_limits(const double *r, double *dt_lim) {
 // afh_fluid_fetch_step
 static int32_t flux_tree_ions(afh_fluid *f, int32_t s_deriv, double *dt_lim, bool fetch);
 
+// bc_to_gc2 has no af_bc_continuous case: the reference error-stops on a flux
+// species with such a face (m_af_ghostcell.f90:317-318, "unsupported boundary
+// condition"). Checked on the host before the step's first launch.
+static int32_t flux_bc_check(const afh_fluid *f, int32_t s_deriv) {
+  afh_tree *t = f->t;
+  for (int q = -1; q < f->d.n_ions; q++) {
+    const int iv =
+        (q < 0 ? f->d.i_electron : f->d.species_iv[f->d.ion_species[q] - 1]) + s_deriv;
+    if (int32_t e = check_iv(t, iv, "afh_flux_upwind_tree")) return e;
+    for (int nb = 0; nb < 4; nb++)
+      if (!t->periodic[nb >> 1] && t->meth[iv].bc[nb].type == AFH_BC_CONTINUOUS)
+        return set_error(AFH_ERR_UNSUPPORTED, "flux: bc type %d on variable %d",
+                         AFH_BC_CONTINUOUS, iv);
+  }
+  return AFH_OK;
+}
+
 static int32_t flux_tree(afh_fluid *f, int32_t s_deriv, double *dt_lim, bool fetch = true) {
   afh_tree *t = f->t;
+  if (int32_t ebc = flux_bc_check(f, s_deriv)) return ebc;
   if (f->d.n_ions > 0) return flux_tree_ions(f, s_deriv, dt_lim, fetch);
   const int iv = f->d.i_electron + s_deriv;
   if (int32_t e = check_iv(t, iv, "afh_flux_upwind_tree")) return e;

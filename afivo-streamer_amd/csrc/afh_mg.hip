@@ -3943,8 +3943,24 @@ static int32_t solve_coarse_pfmg(afh_mg *mg) {
   return gc_lvl(t, 1, mg->d.i_phi, 1);
 }
 
+// The level-1 solve takes Dirichlet and Neumann faces only: the reference
+// error-stops on any other type (m_coarse_solver.f90:485-486, "unsupported
+// boundary condition"). Every solve checks before its first launch, so a type
+// set by a later afh_set_bc is caught too and the refused call changes nothing.
+static int32_t phi_bc_check(const afh_mg *mg) {
+  const afh_tree *t = mg->t;
+  const afh_bc *bc = t->meth[mg->d.i_phi].bc;
+  for (int q = 0; q < 6; q++) {
+    if (t->periodic[q >> 1]) continue;  // (never read)
+    if (bc[q].type != AFH_BC_DIRICHLET && bc[q].type != AFH_BC_NEUMANN)
+      return set_error(AFH_ERR_UNSUPPORTED, "coarse solve: bc type %d", bc[q].type);
+  }
+  return AFH_OK;
+}
+
 static int32_t solve_coarse(afh_mg *mg) {
   afh_tree *t = mg->t;
+  if (int32_t e = phi_bc_check(mg)) return e;
   if (mg->d.coarse_mode == AFH_COARSE_PFMG) return solve_coarse_pfmg(mg);
   if (mg->any_var && mg->lvl_var[0]) return solve_coarse_gs(mg);
   CsParams &P = mg->P;
@@ -4090,6 +4106,7 @@ int32_t afh_mg_fas_fmg(afh_mg *mg, int32_t set_residual, int32_t have_guess) {
   if (!mg) return set_error(AFH_ERR_ARG, "null mg");
   afh_tree *t = mg->t;
   AFH_LIVE(t, "afh_mg_fas_fmg");
+  if (int32_t ebc = phi_bc_check(mg)) return ebc;
   t->touch(mg->d.i_phi), t->touch(mg->d.i_rhs), t->touch(mg->d.i_tmp);
   const int nl = t->nlvl, i_phi = mg->d.i_phi;
   double *phi = t->ccv(i_phi), *tmp = t->ccv(mg->d.i_tmp);
@@ -4352,6 +4369,7 @@ static int32_t vcycle_impl(afh_mg *mg, int32_t set_residual, int32_t hl, bool ma
   if (!mg) return set_error(AFH_ERR_ARG, "null mg");
   afh_tree *t = mg->t;
   AFH_LIVE(t, "afh_mg_fas_vcycle");
+  if (int32_t ebc = phi_bc_check(mg)) return ebc;
   const bool top_stale = mg->phi_gc_gen != t->gen[mg->d.i_phi];
   t->touch(mg->d.i_phi), t->touch(mg->d.i_rhs), t->touch(mg->d.i_tmp);
   const int max_lvl = (hl > 0 && hl <= t->nlvl) ? hl : t->nlvl;

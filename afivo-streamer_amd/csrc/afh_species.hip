@@ -2710,6 +2710,23 @@ extern "C" {
 
 }  // extern "C"
 
+// bc_to_gc2 has no af_bc_continuous case: the reference error-stops on a flux
+// species with such a face (m_af_ghostcell.f90:317-318, "unsupported boundary
+// condition"). Checked on the host before the step's first launch.
+static int32_t flux_bc_check(const afh_fluid *f, int32_t s_deriv) {
+  const afh_tree *t = f->t;
+  for (int q = -1; q < f->d.n_ions; q++) {
+    const int iv =
+        (q < 0 ? f->d.i_electron : f->d.species_iv[f->d.ion_species[q] - 1]) + s_deriv;
+    if (iv < 1 || iv > t->nvc) return set_error(AFH_ERR_ARG, "bad s_deriv");
+    for (int nb = 0; nb < 6; nb++)
+      if (!t->periodic[nb >> 1] && t->meth[iv].bc[nb].type == AFH_BC_CONTINUOUS)
+        return set_error(AFH_ERR_UNSUPPORTED, "flux: bc type %d on variable %d",
+                         AFH_BC_CONTINUOUS, iv);
+  }
+  return AFH_OK;
+}
+
 // flux_upwind_tree's device work up to the folded CFL / sigma maxima
 // (reduction slots 0, 1); the caller fetches them
 static int32_t flux_tree_dev(afh_fluid *f, int32_t s_deriv) {
@@ -2717,6 +2734,7 @@ static int32_t flux_tree_dev(afh_fluid *f, int32_t s_deriv) {
   const int nc = t->nc, n3 = nc * nc * nc;
   const int iv = f->d.i_electron + s_deriv;
   if (iv < 1 || iv > t->nvc) return set_error(AFH_ERR_ARG, "bad s_deriv");
+  if (int32_t ebc = flux_bc_check(f, s_deriv)) return ebc;
   t->touch(iv);  // ghost layers written back
   int32_t e;
   if ((e = flux_prelude(f, iv, t->gc2))) return e;
@@ -3118,6 +3136,7 @@ static int32_t fe_dev(afh_fluid *f, double dt, int32_t s_deriv, int32_t n_prev,
   UpdArgs U;
   double upd_bytes;
   int32_t e;
+  if ((e = flux_bc_check(f, s_deriv))) return e;
   if ((e = upd_args(f, dt, s_deriv, n_prev, s_prev, w_prev, s_out, last_step, U,
                     upd_bytes)))
     return e;

@@ -38,7 +38,19 @@ extern "C" {
 #define AFH_ERR_DEVICE -3
 #define AFH_ERR_STATE -4
 
-/* Boundary-condition types, afivo/src/m_af_types.f90:51-64 */
+/* Boundary-condition types, afivo/src/m_af_types.f90:51-64. afh_gc_tree fills
+ * a face of any of the four (bc_to_gc, m_af_ghostcell.f90:173-279). Two users
+ * take fewer, as the reference does, on the faces of a non-periodic dimension:
+ *  - the potential of a multigrid: Dirichlet and Neumann only. Every solve
+ *    (afh_mg_fas_vcycle*, afh_mg_fas_fmg) with another type on the potential
+ *    returns AFH_ERR_UNSUPPORTED ("coarse solve: bc type <n>") before it
+ *    changes anything; the check is made at the solve, so a type set by a
+ *    later afh_set_bc is caught (m_coarse_solver.f90:485-486 error-stops).
+ *  - a flux species (the electrons and every mobile ion): not
+ *    AFH_BC_CONTINUOUS. afh_flux_upwind_tree and afh_fluid_forward_euler[_fold]
+ *    return AFH_ERR_UNSUPPORTED ("flux: bc type -12 on variable <iv>") before
+ *    any launch: bc_to_gc2 has no such case and the reference error-stops
+ *    (m_af_ghostcell.f90:317-318). */
 #define AFH_BC_DIRICHLET -10
 #define AFH_BC_NEUMANN -11
 #define AFH_BC_CONTINUOUS -12

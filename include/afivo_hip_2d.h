@@ -86,6 +86,13 @@
  * regression-log sums and extrema, and the deferred reductions
  * (afh_mg_fas_vcycle_fold, afh_fluid_forward_euler_fold,
  * afh_fluid_fetch_step, below).
+ * Boundary types (the AFH_BC_* of afivo_hip.h, with its two rules): the
+ * potential of a multigrid takes Dirichlet and Neumann faces only, every
+ * solve with another type returns AFH_ERR_UNSUPPORTED ("2-D coarse solve: bc
+ * type <n>"; m_coarse_solver.f90:485-486); a flux species with a non-periodic
+ * AFH_BC_CONTINUOUS face makes afh_flux_upwind_tree and
+ * afh_fluid_forward_euler[_fold] return AFH_ERR_UNSUPPORTED before any launch
+ * (bc_to_gc2 has no such case, m_af_ghostcell.f90:317-318).
  */
 #ifndef AFIVO_HIP_2D_H
 #define AFIVO_HIP_2D_H

@@ -1718,10 +1718,25 @@ int32_t afo_mg_pfmg_operator(afh_mg *mg, int32_t *dims, double *a7) {
   return AFH_OK;
 }
 
+/* The level-1 solve takes Dirichlet and Neumann faces only: the reference
+ * error-stops on any other type (m_coarse_solver.f90:485-486, "unsupported
+ * boundary condition"). Checked by every solve before it changes anything,
+ * so a type set by a later afo_set_bc is caught too. */
+static int32_t mg_bc_check(const afh_mg *mg) {
+  for (int q = 0; q < 6; q++) {
+    int ty = mg->t->meth[mg->d.i_phi].bc[q].type;
+    if (ty != AFH_BC_DIRICHLET && ty != AFH_BC_NEUMANN)
+      return fail(AFH_ERR_UNSUPPORTED, "coarse solve: bc type %d", ty);
+  }
+  return AFH_OK;
+}
+
 /* solve_coarse_grid, m_af_multigrid.f90:266-291 */
 int32_t afo_mg_solve_coarse(afh_mg *mg) {
   afh_tree *t = mg->t;
   int nc = t->nc, nid = LVL_N(t, ids, 1);
+  int32_t e = mg_bc_check(mg);
+  if (e) return e;
   if (mg->d.coarse_mode == AFH_COARSE_PFMG) return solve_coarse_pfmg(mg);
   for (int q = 0; q < t->nb; q++)
     if (mg->vst[q] && B(t, q + 1)->lvl == 1) return solve_coarse_gs(mg);
@@ -1964,6 +1979,8 @@ int32_t afo_mg_set_box_lsf(afh_mg *mg, int32_t id, int32_t n, const int32_t *ix,
 int32_t afo_mg_fas_vcycle(afh_mg *mg, int32_t set_residual, int32_t hl) {
   LIVE(mg->t);
   afh_tree *t = mg->t;
+  int32_t ebc = mg_bc_check(mg);
+  if (ebc) return ebc;
   touch(t, mg->d.i_phi), touch(t, mg->d.i_rhs), touch(t, mg->d.i_tmp);
   int max_lvl = (hl > 0) ? hl : t->nlvl;
   for (int lvl = max_lvl; lvl >= 2; lvl--) {
@@ -2019,6 +2036,8 @@ int32_t afo_tree_fetch_reduced(afh_tree *t, int32_t n, const int32_t *slots, dou
 int32_t afo_mg_fas_fmg(afh_mg *mg, int32_t set_residual, int32_t have_guess) {
   LIVE(mg->t);
   afh_tree *t = mg->t;
+  int32_t ebc = mg_bc_check(mg);
+  if (ebc) return ebc;
   touch(t, mg->d.i_phi), touch(t, mg->d.i_rhs), touch(t, mg->d.i_tmp);
   int nl = t->nlvl, i_phi = mg->d.i_phi, i_tmp = mg->d.i_tmp;
   size_t bsz = t->bsz;
@@ -2753,6 +2772,15 @@ int32_t afo_flux_upwind_tree(afh_fluid *f, int32_t s_deriv, double *dt_lim) {
   LIVE(f->t);
   afh_tree *t = f->t;
   int nc = t->nc;
+  /* bc_to_gc2 has no af_bc_continuous case: the reference error-stops
+   * (m_af_ghostcell.f90:317-318, "unsupported boundary condition") */
+  for (int q = -1; q < f->d.n_ions; q++) {
+    const int iv = (q < 0 ? f->d.i_electron : f->d.species_iv[f->d.ion_species[q] - 1]) + s_deriv;
+    if (iv < 1 || iv > t->nvc) return fail(AFH_ERR_ARG, "bad s_deriv");
+    for (int nb = 0; nb < 6; nb++)
+      if (t->meth[iv].bc[nb].type == AFH_BC_CONTINUOUS)
+        return fail(AFH_ERR_UNSUPPORTED, "flux: bc type %d on variable %d", AFH_BC_CONTINUOUS, iv);
+  }
   touch(t, f->d.i_electron + s_deriv); /* ghost layers written back */
   if (restrict_ref_boundary(t, f->d.i_electron + s_deriv)) return AFH_ERR_STATE;
   for (int q = 0; q < f->d.n_ions; q++) {

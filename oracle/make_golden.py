@@ -232,9 +232,24 @@ CASES_2D = {
 ONE_FILE = ("uni4", "uni8", "amr4", "rod8", "regrid8", "uni2d", "amr2d")
 
 
+def savez_fixed(path, arrays):
+    """np.savez_compressed with the members' time stamps fixed, so the same
+    arrays give the same file byte for byte."""
+    import io
+    import zipfile
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as z:
+        for k, v in arrays.items():
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(v), allow_pickle=False)
+            info = zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o600 << 16
+            z.writestr(info, buf.getvalue())
+
+
 def save_parts(case, out):
-    """np.savez_compressed of out, the arrays dealt in order over as many
-    files as PART_LIMIT asks for; returns the paths written."""
+    """savez_fixed of out, the arrays dealt in order over as many files as
+    PART_LIMIT asks for; returns the paths written."""
     import glob
     import zlib
     base = os.path.join(REPO, "tests", "golden", case)
@@ -251,7 +266,7 @@ def save_parts(case, out):
     paths = []
     for i, part in enumerate(parts):
         paths.append(base + (".p%d.npz" % i if i else ".npz"))
-        np.savez_compressed(paths[-1], **part)
+        savez_fixed(paths[-1], part)
         assert case in ONE_FILE or os.path.getsize(paths[-1]) <= PART_LIMIT
     return paths
 
