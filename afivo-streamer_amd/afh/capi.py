@@ -224,6 +224,13 @@ SIGNATURES_SRCFAC = {
     "fluid_set_source_factor": (i32, [_VP, i32, C.POINTER(C.c_uint8), f64, i32]),
 }
 SRCFAC_NONE, SRCFAC_FLUX = 0, 1
+# the rate and J.E sums of the last step (include/afivo_hip_rates.h): both
+# HIP libraries have them, the oracle and the common ABI do not
+SIGNATURES_RATES = {
+    "fluid_set_rate_sums": (i32, [_VP, i32]),
+    "fluid_fetch_rate_sums": (i32, [_VP, P_f64, P_f64]),
+}
+SIGNATURES_EXTRA = dict(SIGNATURES_SRCFAC, **SIGNATURES_RATES)
 DIST_LOCAL, DIST_RCCL = 1, 2
 HOOK_HALO, HOOK_RIMS, HOOK_RESTRICT, HOOK_MAX, HOOK_MIN, HOOK_CFLUX = 1, 2, 3, 4, 5, 6
 HOOK_SUM = 7
@@ -297,7 +304,7 @@ _loaded = {}
 def hip_library():
     """The product library. Raises if it was not built -- no CPU fallback."""
     if "hip" not in _loaded:
-        _loaded["hip"] = Library(HIP_LIB, "afh_", extra=SIGNATURES_SRCFAC)
+        _loaded["hip"] = Library(HIP_LIB, "afh_", extra=SIGNATURES_EXTRA)
     return _loaded["hip"]
 
 
@@ -307,7 +314,7 @@ def hip_library_2d():
     if "hip2d" not in _loaded:
         only = [n[len("afh_"):] for n in header_symbols("afivo_hip_2d.h")]
         _loaded["hip2d"] = Library(HIP_LIB_2D, "afh_",
-                                   extra=dict(SIGNATURES_2D, **SIGNATURES_SRCFAC), only=only)
+                                   extra=dict(SIGNATURES_2D, **SIGNATURES_EXTRA), only=only)
     return _loaded["hip2d"]
 
 

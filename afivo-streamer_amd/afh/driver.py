@@ -122,8 +122,12 @@ class Simulation:
     """One streamer simulation (src/streamer.f90) over a C-ABI library."""
 
     def __init__(self, lib, case, device=-1, coarse_cycles=0, capacity_factor=2.0,
-                 fuse_rhs=True, user=None, coarse_tol=0.0, coarse_mode=None):
-        """user: the program's m_user hooks (afh.users), e.g. the gas density
+                 fuse_rhs=True, user=None, coarse_tol=0.0, coarse_mode=None,
+                 global_rates=False):
+        """global_rates: keep ST_global_rates, ST_global_JdotE and Sato's
+        currents (streamer.f90:290-317) from the sums of every accepted
+        step's last sub-step (include/afivo_hip_rates.h); diagnostics().
+        user: the program's m_user hooks (afh.users), e.g. the gas density
         function and initial conditions of programs/3d_sprite.
         coarse_cycles / coarse_tol: the level-1 solve (0: exact; else at most
         coarse_cycles MG cycles, stopped at |r| < coarse_tol |b| when
@@ -314,6 +318,21 @@ class Simulation:
                     raise ValueError("write_source_factor: no cc variable named srcfac "
                                      "in cc_names")
                 self.i_srcfac = self.cc_names.index("srcfac") + 1
+        # ST_global_rates, ST_global_JdotE and the currents of Sato's equation
+        # (streamer.f90:290-317); current_update_per_steps: optional in the
+        # case dict, else the reference's default (m_streamer.f90:169)
+        self.rate_sums = bool(global_rates)
+        if self.rate_sums and not lib.has("fluid_set_rate_sums"):
+            raise NotImplementedError(
+                "global_rates: the rate and J.E sums are not built in this library "
+                "(include/afivo_hip_rates.h: the HIP libraries)")
+        self.global_rates = np.zeros(len(self.reactions))
+        self.global_JdotE = 0.0
+        self.JdotE_current = self.displ_current = 0.0
+        self.field_energy = self.field_energy_prev = 0.0
+        self.field_energy_prev_time = 0.0
+        self.current_update_per_steps = c.i("current_update_per_steps") \
+            if "current_update_per_steps" in c.d else 1000 * 1000
         # init conditions (m_init_cond.f90:38-144)
         self.background = c.r("background_density")
         self.seeds = []
@@ -424,6 +443,8 @@ class Simulation:
         if self.source_factor != capi.SRCFAC_NONE:
             self.fluid.set_source_factor(self.source_factor, self.ionization,
                                          self.source_min_electrons, self.i_srcfac)
+        if self.rate_sums:
+            self.fluid.set_rate_sums(True)
         if self.fused_rhs:
             self.fluid.set_rhs_output(self.i_rhs, True)
         self.faces_from_phi = self._faces_from_phi_ok and self.lsf is None
@@ -511,6 +532,9 @@ class Simulation:
         same state before (e.g. the same deterministic set-up). A refinement
         of the sharded run (adjust_refinement) needs the library's own
         sharding (afh.dist.NativeShard); with the Python Shard it raises."""
+        if self.rate_sums:
+            raise NotImplementedError("global_rates: the sums over the ranks of a sharded "
+                                      "run are not built (include/afivo_hip_rates.h)")
         if any(self.periodic):
             raise NotImplementedError("a periodic case cannot run sharded: the partition "
                                       "plans are built from geometry (afh_tree_create_sharded)")
@@ -1153,6 +1177,8 @@ class Simulation:
         else:
             raise RuntimeError("All time steps were rejected")
         self.frac_rejected = 0.99 * self.frac_rejected + (0.01 if n > 1 else 0.0)
+        if self.rate_sums:
+            self._accumulate_rates()
         self.field_compute(0, True)
         tmp = self.dt_growth if self.frac_rejected <= 0.1 else 1.0
         self.dt = min(tmp * self.global_dt, self.dt_safety * min(dt_lim, self.dt_max))
@@ -1180,6 +1206,50 @@ class Simulation:
                     self.photoi_prev_time = self.time
         return True
 
+    def compute_field_energy(self):
+        """field_compute_energy (src/m_field.f90:764-800) without a
+        dielectric: 0.5 eps0 times the volume integral of |E|**2 (the
+        reduction carries the 2 pi r weight of a cylindrical tree)."""
+        return 0.5 * UC_EPS0 * self.tree.sum_cc(self.i_efld, 2)
+
+    def _accumulate_rates(self):
+        """After an accepted step (streamer.f90:290-317): the sums of its last
+        sub-step times dt into the global integrals (a rejected attempt's sums
+        are overwritten by the next one's), and every current_update_per_steps
+        iterations the currents of Sato's equation."""
+        rates, jde = self.fluid.fetch_rate_sums()
+        self.global_rates = self.global_rates + rates * self.dt
+        self.global_JdotE = self.global_JdotE + jde * self.dt
+        if self.it % self.current_update_per_steps == 0:
+            self.field_energy = self.compute_field_energy()
+            tmp = (self.field_energy - self.field_energy_prev) \
+                / (self.time - self.field_energy_prev_time)
+            self.field_energy_prev = self.field_energy
+            self.field_energy_prev_time = self.time
+            if abs(self.voltage) > 0.0:
+                self.JdotE_current = jde / self.voltage
+                self.displ_current = tmp / self.voltage
+            else:
+                self.JdotE_current = self.displ_current = 0.0
+
+    def _field_energy_start(self):
+        """streamer.f90:174-175."""
+        if self.rate_sums:
+            self.field_energy_prev = self.compute_field_energy()
+            self.field_energy_prev_time = self.time
+
+    def diagnostics(self):
+        """The integrals of Simulation(..., global_rates=True): ST_global_rates
+        (events per reaction), ST_global_JdotE (J), the two currents of Sato's
+        equation (A) and the field energy they were formed with (J)."""
+        if not self.rate_sums:
+            raise RuntimeError("diagnostics: the run was created without global_rates")
+        return {"global_rates": self.global_rates.copy(),
+                "global_JdotE": self.global_JdotE,
+                "JdotE_current": self.JdotE_current,
+                "displ_current": self.displ_current,
+                "field_energy": self.field_energy}
+
     def clone(self, lib, device=-1):
         """The same simulation state on another library (e.g. the C oracle
         for a CPU baseline): topology, every cell and face variable, time."""
@@ -1205,10 +1275,9 @@ class Simulation:
         """af_write_tree(tree, name, write_sim_data) as the streamer's output
         does (m_af_output.f90:41-194, streamer.f90:521-536): the topology of
         the host tree, every cell and face variable from the device, the
-        simulation record appended; writes name + ".dat". The global
-        reaction rates and J.E integrals (ST_global_rates / JdotE, outputs of
-        the reference's analysis module, not computed here) are written as
-        zeros."""
+        simulation record appended; writes name + ".dat". The record holds
+        ST_global_rates and ST_global_JdotE as the run has accumulated them
+        (zero in a run without global_rates, unless a restart read them)."""
         from .datfile import DatTree, sim_data_bytes
         if self.faces_from_phi:
             # the face field the reference stores: mg_box_lpl_gradient of the
@@ -1226,7 +1295,7 @@ class Simulation:
                 t.boxes[b].fc[iv] = a[b - 1]
         t.other = sim_data_bytes(self.it, self.output_cnt, self.time, self.global_time,
                                  self.photoi_prev_time, self.global_dt,
-                                 np.zeros(len(self.reactions)), 0.0, self.frac_rejected)
+                                 self.global_rates, self.global_JdotE, self.frac_rejected)
         t.write(name + ".dat")
         return t
 
@@ -1262,8 +1331,11 @@ class Simulation:
         self.time, self.global_time = d["time"], d["global_time"]
         self.photoi_prev_time, self.global_dt = d["photoi_prev_time"], d["global_dt"]
         self.frac_rejected = d["fraction_steps_rejected"]
+        self.global_rates = np.array(d["global_rates"], float).reshape(len(self.reactions))
+        self.global_JdotE = float(d["global_JdotE"])
         self.dt = self.global_dt
         self.time_last_output = self.time  # streamer.f90:172
+        self._field_energy_start()
         return t
 
     def start(self):
@@ -1271,6 +1343,7 @@ class Simulation:
         self.output_cnt = 0
         self.output_write()
         self.time_last_output = self.time
+        self._field_energy_start()
 
     def run(self, max_steps=None):
         self.start()

@@ -573,6 +573,21 @@ class Fluid:
         self.lib.call("fluid_set_source_factor", self.h, int(mode), flags,
                       float(min_electrons), int(i_srcfac))
 
+    def set_rate_sums(self, on=True):
+        """afh_fluid_set_rate_sums: every update with last_step also sums the
+        reaction rates and J.E over the leaves (chemical_rates_box,
+        sum_global_JdotE); fetch_rate_sums reads them."""
+        self.lib.call("fluid_set_rate_sums", self.h, int(bool(on)))
+
+    def fetch_rate_sums(self):
+        """(rates[n_reactions], J.E) of the most recent last step
+        (afh_fluid_fetch_rate_sums): ST_current_rates and ST_current_JdotE."""
+        rates = np.zeros(max(self.n_reactions, 1))
+        jde = C.c_double()
+        self.lib.call("fluid_fetch_rate_sums", self.h,
+                      rates.ctypes.data_as(C.POINTER(C.c_double)), C.byref(jde))
+        return rates[:self.n_reactions].copy(), jde.value
+
     def ion_se_flux(self):
         """handle_ion_se_flux over the leaves (afh_fluid_ion_se_flux)."""
         self.lib.call("fluid_ion_se_flux", self.h)

@@ -58,11 +58,15 @@
 // variable half-sweep (924-934), is a kernel of its own: every cell's rhs
 // makes the bc_correction round trip, one thread per cell. The fused pair is
 // k2_pair_box<NC, LPB, CYL, VAR>, the species update k2_update<NS, CYL, PHOTO,
-// MASK, IONS, SRCFAC>.
+// MASK, IONS, SRCFAC, RATES>.
 //
 // The flux-based source factor (afh_fluid_set_source_factor, include/
 // afivo_hip_srcfac.h): SRCFAC of the update (compute_source_factor,
 // src/m_fluid.f90:525-583, and its use at 368-397).
+//
+// The rate and J.E sums of a last step (afh_fluid_set_rate_sums, include/
+// afivo_hip_rates.h): RATES of the update (chemical_rates_box and
+// sum_global_JdotE, src/m_fluid.f90:665-731) and k2_rate_fold.
 //
 // Cylindrical coordinates (af_cyl, afh_tree_set_coord): StCyl, CYL of the
 // pair and of the update (m_af_flux_schemes.f90:395-406), k2_consistent_cyl
@@ -105,6 +109,7 @@
 
 #include "../../include/afivo_hip_2d.h"
 #include "../../include/afivo_hip_srcfac.h"
+#include "../../include/afivo_hip_rates.h"
 #include "afh_cs_tables.h"
 #include "afh_pfmg_dev.h"
 
@@ -1614,7 +1619,7 @@ __device__ __forceinline__ double rate_of(const UpdArgs &A, const DevReaction &R
 // species count when it is a compile-time case (the per-cell arrays then stay
 // in registers; wave-uniform indices use VGPR index mode), MAXS for any count
 // (A.ns; the arrays in scratch). One kernel, k2_update<NS, CYL, PHOTO, MASK,
-// IONS, SRCFAC>; a feature that is off is compiled out and its argument block
+// IONS, SRCFAC, RATES>; a feature that is off is compiled out and its argument block
 // is empty (UpdOpt).
 //
 // CYL (a cylindrical tree): the r-fluxes times af_cyl_flux_factors inside the
@@ -1692,24 +1697,77 @@ template <int N = 1, class F> inline void with_species_count(int ns, F &&f) {
   else with_species_count<N + 1>(ns, f);
 }
 
-template <bool PHOTO, bool MASK, bool IONS, bool SRCFAC = false>
-struct UpdOpt : ArgsIf<PHOTO, PhotoArgs, 0>, ArgsIf<MASK, MaskArgs, 1>,
-                ArgsIf<IONS, IonUpdArgs, 2>, ArgsIf<SRCFAC, SrcFacArgs, 3> {};
+// RATES (afh_fluid_set_rate_sums, include/afivo_hip_rates.h; last steps
+// only): the space integrals of the reaction rates and of J.E
+// (chemical_rates_box and sum_global_JdotE, src/m_fluid.f90:665-731). Every
+// workgroup writes one row of nr + 1 doubles (the reactions, then J.E) into
+// R.part, row R.row0 + its index in the launch; k2_rate_fold adds the rows in
+// a fixed order. Every lane runs the cell's arithmetic (a lane without a cell
+// that of the box's first cell, storing nothing and adding +0.0), so the wave
+// sums see 64 active lanes; each reaction's value goes to the wave's LDS slot
+// as it is formed. A box the mask leaves no cell of adds +0.0; of any other
+// box every cell counts, masked ones included.
+struct RateSumArgs {
+  double *part;
+  int row0;
+  const double *Ef;  // face field
+};
 
-template <int NS, bool CYL, bool PHOTO, bool MASK, bool IONS, bool SRCFAC = false>
+// the wave's sum in a fixed order (the xor butterfly: every lane ends with
+// the same bits); every lane of the wave must be active
+__device__ __forceinline__ double wave_sum(double v) {
+  for (int o = 32; o > 0; o >>= 1) v = v + __shfl_xor(v, o, 64);
+  return v;
+}
+// the wave partials of a k2_update<..., RATES> workgroup: [nr + 1][4 waves]
+__device__ __forceinline__ double *rate_sum_lds() {
+  __shared__ double w[(AFH_MAX_REACTIONS + 1) * 4];
+  return w;
+}
+
+// adds the rows of part in a fixed order: one workgroup per column (reaction,
+// J.E), lane q the rows q, q + NT, ... in turn, then the lanes' sums by
+// halving through LDS
+__global__ void __launch_bounds__(NT)
+    k2_rate_fold(const double *__restrict__ part, int n_rows, int n_col,
+                 double *__restrict__ out) {
+  const int c = blockIdx.x;
+  double s = 0.0;
+  for (int r = threadIdx.x; r < n_rows; r += NT) s = s + part[(size_t)r * n_col + c];
+  __shared__ double w[NT];
+  w[threadIdx.x] = s;
+  __syncthreads();
+  for (int h = NT / 2; h > 0; h >>= 1) {
+    if ((int)threadIdx.x < h) w[threadIdx.x] = w[threadIdx.x] + w[threadIdx.x + h];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[c] = w[0];
+}
+
+template <bool PHOTO, bool MASK, bool IONS, bool SRCFAC = false, bool RATES = false>
+struct UpdOpt : ArgsIf<PHOTO, PhotoArgs, 0>, ArgsIf<MASK, MaskArgs, 1>,
+                ArgsIf<IONS, IonUpdArgs, 2>, ArgsIf<SRCFAC, SrcFacArgs, 3>,
+                ArgsIf<RATES, RateSumArgs, 4> {};
+
+template <int NS, bool CYL, bool PHOTO, bool MASK, bool IONS, bool SRCFAC = false,
+          bool RATES = false>
 __global__ void __launch_bounds__(NT)
     k2_update(UpdArgs A, const int32_t *__restrict__ ids, const afh_box_meta *__restrict__ meta,
-              int nc, int bsz, int fsz, UpdOpt<PHOTO, MASK, IONS, SRCFAC> O,
+              int nc, int bsz, int fsz, UpdOpt<PHOTO, MASK, IONS, SRCFAC, RATES> O,
               unsigned long long *red) {
   const ArgsIf<PHOTO, PhotoArgs, 0> &P = O;
   const ArgsIf<MASK, MaskArgs, 1> &M = O;
   const ArgsIf<IONS, IonUpdArgs, 2> &I = O;
   const ArgsIf<SRCFAC, SrcFacArgs, 3> &S = O;
+  const ArgsIf<RATES, RateSumArgs, 4> &R_ = O;
   static_assert(!(CYL && MASK), "the update mask in cylindrical coordinates is not built");
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  const int t_ = blockIdx.x * blockDim.x + threadIdx.x;
   double cmin = 1e100;
   const int ns = NS == MAXS ? A.ns : NS;
-  if (t < nc * nc) {
+  // (without RATES: a lane without a cell skips the body)
+  const bool live = t_ < nc * nc;
+  const int t = RATES && !live ? 0 : t_;
+  if (RATES || live) {
     const int id = ids[blockIdx.y];
     const int i = t % nc + 1, j = t / nc + 1, ng = nc + 2, nf = nc + 1;
     const size_t x = (size_t)(id - 1) * bsz + ix2(ng, i, j);
@@ -1743,7 +1801,14 @@ __global__ void __launch_bounds__(NT)
         if (ne * (m * m * m) < S.min_e) sfac = 0.0;
       }
       // (add_source_terms returns before this for a wholly masked box)
-      if (S.out && src) S.out[x] = sfac;
+      if (S.out && src && (!RATES || live)) S.out[x] = sfac;
+    }
+    // af_cyl_volume_cc (m_af_types.f90:1176-1182), or product(dr)
+    double vol = 0.0;
+    if constexpr (RATES) {
+      const double *dr = meta[id - 1].dr;
+      vol = dr[0] * dr[1];
+      if (CYL) vol = 2 * 3.141592653589793 * (meta[id - 1].r_min[0] + (i - 0.5) * dr[0]) * vol;
     }
     for (int r = 0; r < A.nr; r++) {
       const DevReaction &R = A.reac[r];
@@ -1754,11 +1819,27 @@ __global__ void __launch_bounds__(NT)
       double prod = 1.0;
       for (int q = 0; q < R.n_in; q++) prod = prod * dens[R.ix_in[q] - 1];
       rate = rate * prod;
+      if constexpr (RATES) {
+        // chemical_rates_box: w(i) * rate per cell on a cylindrical tree,
+        // else sum(rates) with product(dr) on the workgroup's sum
+        const double ws = wave_sum(live && src ? (CYL ? vol * rate : rate) : 0.0);
+        if ((threadIdx.x & 63) == 0) rate_sum_lds()[4 * r + (threadIdx.x >> 6)] = ws;
+      }
       for (int q = 0; q < R.n_in; q++) der[R.ix_in[q] - 1] = der[R.ix_in[q] - 1] - rate;
       for (int q = 0; q < R.n_out; q++)
         der[R.ix_out[q] - 1] = der[R.ix_out[q] - 1] + rate * R.mult_out[q];
     }
-    if (A.last_step && src) {
+    if constexpr (RATES) {
+      // sum_global_JdotE: fc_inner_product(flux_elec, electric_fld) times the
+      // cell volume, in the reference's operand order
+      const double *Fe = A.F + (size_t)(id - 1) * fsz, *Ef = R_.Ef + (size_t)(id - 1) * fsz;
+      const int g0 = (j - 1) * nf + (i - 1), g2 = nf * nf;
+      double ip = 0.5 * (Fe[g0] * Ef[g0] + Fe[g2 + g0] * Ef[g2 + g0]);
+      ip = ip + 0.5 * (Fe[g0 + 1] * Ef[g0 + 1] + Fe[g2 + g0 + nf] * Ef[g2 + g0 + nf]);
+      const double ws = wave_sum(live && src ? ip * vol : 0.0);
+      if ((threadIdx.x & 63) == 0) rate_sum_lds()[4 * A.nr + (threadIdx.x >> 6)] = ws;
+    }
+    if (A.last_step && src && (!RATES || live)) {
       const double eps = 1e-100;
 #pragma unroll
       for (int s = 0; s < ns; s++) {
@@ -1815,7 +1896,23 @@ __global__ void __launch_bounds__(NT)
       }
     }
 #pragma unroll
-    for (int s = 0; s < ns; s++) A.out[s][x] = y[s];
+    for (int s = 0; s < ns; s++)
+      if (!RATES || live) A.out[s][x] = y[s];
+  }
+  if constexpr (RATES) {
+    // the workgroup's row: the waves' sums in wave order, then product(dr)
+    // on the rates of a Cartesian box and UC_elec_charge on J.E
+    __syncthreads();
+    for (int c = threadIdx.x; c <= A.nr; c += blockDim.x) {
+      const double *w = rate_sum_lds() + 4 * c;
+      double s = w[0];
+      for (int q = 1; q < (int)(blockDim.x >> 6); q++) s = s + w[q];
+      const double *dr = meta[ids[blockIdx.y] - 1].dr;
+      if (c == A.nr) s = s * -1.6022e-19;
+      else if (!CYL) s = s * (dr[0] * dr[1]);
+      const size_t row = (size_t)R_.row0 + (size_t)blockIdx.y * gridDim.x + blockIdx.x;
+      R_.part[row * (A.nr + 1) + c] = s;
+    }
   }
   if (A.last_step) block_fold<false>(cmin, red);
 }
@@ -2122,6 +2219,12 @@ struct afh_fluid {
   int sf_mode = 0, sf_iv = 0;
   double sf_min_e = 0.0;
   uint8_t *d_sf_ion = nullptr;
+  // afh_fluid_set_rate_sums: on, the workgroups' partial rows (rs_cap rows of
+  // n_reactions + 1 doubles), the folded result on the device and whether a
+  // last step has filled it
+  bool rs_on = false, rs_valid = false;
+  double *d_rs_part = nullptr, *d_rs_out = nullptr;
+  size_t rs_cap = 0;
 };
 
 namespace afh2 {
@@ -3431,6 +3534,7 @@ int32_t afh_fluid_destroy(afh_fluid *f) {
   hipStreamSynchronize(f->t->stream);
   hipFree(f->d_td), hipFree(f->d_chem), hipFree(f->d_reac);
   hipFree(f->d_ids), hipFree(f->d_mstat), hipFree(f->d_gc2), hipFree(f->d_sf_ion);
+  hipFree(f->d_rs_part), hipFree(f->d_rs_out);
   delete f;
   return AFH_OK;
 }
@@ -3647,6 +3751,26 @@ static int32_t flux_tree_ions(afh_fluid *f, int32_t s_deriv, double *dt_lim, boo
   return AFH_OK;
 }
 
+// the partial rows of a last step with the rate sums on: one per update
+// workgroup of every leaf
+static int32_t rate_sums_reserve(afh_fluid *f) {
+  afh_tree *t = f->t;
+  const size_t rows = (size_t)(t->leaves.off[t->nlvl] - t->leaves.off[0]) *
+                      grid2(t->nc * t->nc, 1).x;
+  const size_t ncol = (size_t)f->d.n_reactions + 1;
+  if (!f->d_rs_out) H2(hipMalloc(&f->d_rs_out, ncol * sizeof(double)));
+  if (rows > f->rs_cap) {
+    // (a queued fold may still read the old rows)
+    H2(hipStreamSynchronize(t->stream));
+    hipFree(f->d_rs_part);
+    f->d_rs_part = nullptr;
+    f->rs_cap = 0;
+    H2(hipMalloc(&f->d_rs_part, rows * ncol * sizeof(double)));
+    f->rs_cap = rows;
+  }
+  return AFH_OK;
+}
+
 // fetch = false: the chemistry minimum stays in slot 2 (last step)
 static int32_t update(afh_fluid *f, double dt, int32_t s_deriv, int32_t n_prev,
                       const int32_t *s_prev, const double *w_prev, int32_t s_out,
@@ -3700,6 +3824,11 @@ static int32_t update(afh_fluid *f, double dt, int32_t s_deriv, int32_t n_prev,
       H2_LAUNCH("k2_mask_status");
     }
   }
+  // the rate sums (afh_fluid_set_rate_sums): last steps only
+  const bool rates = f->rs_on && A.last_step;
+  const int upd_gx = (int)grid2(t->nc * t->nc, 1).x;
+  if (rates)
+    if (int32_t e = rate_sums_reserve(f)) return e;
   for (int l = 1; l <= t->nlvl; l++) {
     const int n = t->leaves.n(l);
     if (!n) continue;
@@ -3707,6 +3836,8 @@ static int32_t update(afh_fluid *f, double dt, int32_t s_deriv, int32_t n_prev,
     const dim3 bk = blk2(t->nc * t->nc);
     const int32_t *ids = t->leaves.at(l);
     unsigned long long *red = t->red + 2 * RED_SHARDS;
+    const RateSumArgs RS{f->d_rs_part, (t->leaves.off[l - 1] - t->leaves.off[0]) * upd_gx,
+                         t->fcv(f->d.f_field)};
     // the argument blocks of the features (the launch takes those that are on)
     const bool photo = f->d.i_photo > 0, mask = M.lsf != nullptr, ions = f->d.n_ions > 0;
     const PhotoArgs P{photo ? t->ccv(f->d.i_photo) : nullptr, f->d.photo_species - 1};
@@ -3726,16 +3857,20 @@ static int32_t update(afh_fluid *f, double dt, int32_t s_deriv, int32_t n_prev,
         with_flag(photo, [&](auto photo_) {
           with_flag(ions, [&](auto ions_) {
             with_flag(srcfac, [&](auto srcfac_) {
-              constexpr bool C = decltype(cyl_)::value, PH = decltype(photo_)::value,
-                             MK = decltype(mask_)::value, IO = decltype(ions_)::value,
-                             SF = decltype(srcfac_)::value;
-              UpdOpt<PH, MK, IO, SF> O;
-              if constexpr (PH) static_cast<PhotoArgs &>(O) = P;
-              if constexpr (MK) static_cast<MaskArgs &>(O) = M;
-              if constexpr (IO) static_cast<IonUpdArgs &>(O) = I;
-              if constexpr (SF) static_cast<SrcFacArgs &>(O) = S;
-              hipLaunchKernelGGL((k2_update<decltype(ns)::value, C, PH, MK, IO, SF>), g, bk, 0,
-                                 t->stream, A, ids, t->d_boxes, t->nc, t->bsz, t->fsz, O, red);
+              with_flag(rates, [&](auto rates_) {
+                constexpr bool C = decltype(cyl_)::value, PH = decltype(photo_)::value,
+                               MK = decltype(mask_)::value, IO = decltype(ions_)::value,
+                               SF = decltype(srcfac_)::value, RT = decltype(rates_)::value;
+                UpdOpt<PH, MK, IO, SF, RT> O;
+                if constexpr (PH) static_cast<PhotoArgs &>(O) = P;
+                if constexpr (MK) static_cast<MaskArgs &>(O) = M;
+                if constexpr (IO) static_cast<IonUpdArgs &>(O) = I;
+                if constexpr (SF) static_cast<SrcFacArgs &>(O) = S;
+                if constexpr (RT) static_cast<RateSumArgs &>(O) = RS;
+                hipLaunchKernelGGL((k2_update<decltype(ns)::value, C, PH, MK, IO, SF, RT>), g, bk,
+                                   0, t->stream, A, ids, t->d_boxes, t->nc, t->bsz, t->fsz, O,
+                                   red);
+              });
             });
           });
         });
@@ -3745,6 +3880,13 @@ static int32_t update(afh_fluid *f, double dt, int32_t s_deriv, int32_t n_prev,
       else kind(std::false_type{}, std::false_type{});
     });
     H2_LAUNCH("k2_update");
+  }
+  if (rates) {
+    const int rows = (t->leaves.off[t->nlvl] - t->leaves.off[0]) * upd_gx;
+    hipLaunchKernelGGL(k2_rate_fold, dim3(A.nr + 1), dim3(NT), 0, t->stream, f->d_rs_part, rows,
+                       A.nr + 1, f->d_rs_out);
+    H2_LAUNCH("k2_rate_fold");
+    f->rs_valid = true;
   }
   dt_lim[0] = 1e100, dt_lim[1] = 1e100;
   if (A.last_step && fetch) return red_read(t, 2, 1, 0, dt_lim);
@@ -3841,6 +3983,40 @@ int32_t afh_fluid_set_source_factor(afh_fluid *f, int32_t mode, const uint8_t *i
   f->sf_mode = mode;
   f->sf_min_e = min_electrons_per_cell;
   f->sf_iv = i_srcfac;
+  return AFH_OK;
+}
+
+// (the 2-D library has no sharded trees: AFH_ERR_UNSUPPORTED does not arise)
+int32_t afh_fluid_set_rate_sums(afh_fluid *f, int32_t on) {
+  if (!f) return set_error(AFH_ERR_ARG, "afh_fluid_set_rate_sums: null");
+  afh_tree *t = f->t;
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  H2(hipStreamIsCapturing(t->stream, &cs));
+  if (cs != hipStreamCaptureStatusNone)
+    return set_error(AFH_ERR_STATE, "afh_fluid_set_rate_sums during a graph capture");
+  if (on && !f->rs_on) {
+    if (int32_t e = rate_sums_reserve(f)) return e;
+    f->rs_valid = false;
+  }
+  f->rs_on = on != 0;
+  return AFH_OK;
+}
+
+int32_t afh_fluid_fetch_rate_sums(afh_fluid *f, double *rates, double *jdote) {
+  if (!f || !jdote || (!rates && f->d.n_reactions > 0))
+    return set_error(AFH_ERR_ARG, "afh_fluid_fetch_rate_sums: null");
+  afh_tree *t = f->t;
+  if (!f->rs_on) return set_error(AFH_ERR_STATE, "afh_fluid_fetch_rate_sums: the sums are off");
+  if (!f->rs_valid)
+    return set_error(AFH_ERR_STATE,
+                     "afh_fluid_fetch_rate_sums: no last step since the sums were switched on");
+  const int nr = f->d.n_reactions;
+  std::vector<double> h(nr + 1);
+  H2(hipMemcpyAsync(h.data(), f->d_rs_out, (nr + 1) * sizeof(double), hipMemcpyDeviceToHost,
+                    t->stream));
+  H2(hipStreamSynchronize(t->stream));
+  for (int r = 0; r < nr; r++) rates[r] = h[r];
+  *jdote = h[nr];
   return AFH_OK;
 }
 

@@ -16,7 +16,10 @@
 //                   get_derivatives (m_af_flux_schemes.f90:320-436,
 //                   src/m_fluid.f90:298-466, src/m_chemistry.f90:565-688);
 //                   its SF instantiations with compute_source_factor
-//                   (src/m_fluid.f90:525-583, afh_fluid_set_source_factor)
+//                   (src/m_fluid.f90:525-583, afh_fluid_set_source_factor),
+//                   its RS instantiations with chemical_rates_box and
+//                   sum_global_JdotE (665-731, afh_fluid_set_rate_sums)
+//   k_rate_fold     the workgroups' rate and J.E rows added in a fixed order
 #include <algorithm>
 #include <type_traits>
 #include <utility>
@@ -24,6 +27,7 @@
 #include "afh_internal.h"
 #include "afh_networks.h"
 #include "../../include/afivo_hip_srcfac.h"
+#include "../../include/afivo_hip_rates.h"
 
 namespace afh {
 
@@ -685,6 +689,61 @@ struct UpdArgsSf : UpdArgs {
   SrcFacArgs sf;
 };
 
+// The space integrals of the last step (afh_fluid_set_rate_sums, include/
+// afivo_hip_rates.h: chemical_rates_box and sum_global_JdotE, src/m_fluid.f90:
+// 665-731): only the k_update<..., RS = true> instantiations take these
+// arguments. Every workgroup writes one row of nr + 1 doubles (the reactions,
+// then J.E) into part; k_rate_fold adds the rows in row order.
+struct RateSumArgs {
+  double *part;
+  int row0;           // the row of this launch's workgroup (0, 0)
+  const double *Ef;   // face field, or with phi set fac / dr * (phi_f - phi_{f-1})
+  const double *phi;  // as the flux kernels form it (FluxArgs::phi, gfac)
+  double fac;
+  double gfac[3];     // fac / dr of this level (without UpdArgs::meta)
+  double dr[3];       // dr of this level (without UpdArgs::meta)
+};
+struct UpdArgsRs : UpdArgs {
+  RateSumArgs rs;
+};
+struct UpdArgsSfRs : UpdArgsSf {
+  RateSumArgs rs;
+};
+template <bool SF, bool RS>
+using UpdArgsOf = std::conditional_t<RS, std::conditional_t<SF, UpdArgsSfRs, UpdArgsRs>,
+                                     std::conditional_t<SF, UpdArgsSf, UpdArgs>>;
+
+// the wave's sum in a fixed order (the xor butterfly: every lane ends with
+// the same bits); every lane of the wave must be active
+__device__ __forceinline__ double wave_sum(double v) {
+  for (int o = 32; o > 0; o >>= 1) v = v + __shfl_xor(v, o, 64);
+  return v;
+}
+// the wave partials of a k_update<..., RS> workgroup: [nr + 1][4 waves]
+__device__ __forceinline__ double *rate_sum_lds() {
+  __shared__ double w[(AFH_MAX_REACTIONS + 1) * 4];
+  return w;
+}
+
+// adds the rows of part in a fixed order: one workgroup per column (reaction,
+// J.E), lane q the rows q, q + 256, ... in turn, then the lanes' sums by
+// halving through LDS
+__global__ void __launch_bounds__(256)
+    k_rate_fold(const double *__restrict__ part, int n_rows, int n_col,
+                double *__restrict__ out) {
+  const int c = blockIdx.x;
+  double s = 0.0;
+  for (int r = threadIdx.x; r < n_rows; r += 256) s = s + part[(size_t)r * n_col + c];
+  __shared__ double w[256];
+  w[threadIdx.x] = s;
+  __syncthreads();
+  for (int h = 128; h > 0; h >>= 1) {
+    if ((int)threadIdx.x < h) w[threadIdx.x] = w[threadIdx.x] + w[threadIdx.x + h];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[c] = w[0];
+}
+
 // NORM2 of (a, b, c) as the Fortran runtime of the reference build evaluates
 // it (element by element: the largest magnitude m so far, s = the sum of
 // (x / m)^2 over the others, rescaled when m grows; m sqrt(1 + s)) -- not
@@ -1293,12 +1352,20 @@ __global__ void k_consistent(double *__restrict__ F,
 #endif
 // SF: the source factor (SrcFacArgs) scales the flagged reactions' rates;
 // with the generic reaction loop only (launch_update)
+// RS: the rate and J.E sums of a last step (RateSumArgs), with the generic
+// reaction loop only. Every lane of the workgroup runs the cell's arithmetic
+// (a lane without a cell that of the box's first cell, storing nothing and
+// adding +0.0), so that the wave sums see 64 active lanes; each reaction's
+// value goes to the wave's LDS slot as it is formed (no per-thread array of
+// nr sums), and after the cells the first nr + 1 lanes add the waves' slots in
+// wave order into the workgroup's row.
 template <int NS, bool SLOW, int NP = MAXPREV, bool SD = true, bool GAS = false,
-          class NET = void, bool SF = false>
+          class NET = void, bool SF = false, bool RS = false>
 __global__ void __launch_bounds__(256, AFH_UPD_MINW)
-    k_update(std::conditional_t<SF, UpdArgsSf, UpdArgs> A, const int32_t *__restrict__ ids,
+    k_update(UpdArgsOf<SF, RS> A, const int32_t *__restrict__ ids,
              int nc, size_t bsz, size_t fsz, unsigned long long *red) {
   static_assert(!SF || std::is_void<NET>::value, "the source factor takes the generic loop");
+  static_assert(!RS || std::is_void<NET>::value, "the rate sums take the generic loop");
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   const int id = ids[blockIdx.y];
   double cmin = 1e100, rmax = 0.0;
@@ -1306,11 +1373,13 @@ __global__ void __launch_bounds__(256, AFH_UPD_MINW)
   // once (the high face of cell k is the low face of cell k + 1)
   constexpr int KC = AFH_UPD_KC;
   double fz_carry = 0.0;
+  // (without RS: a lane without a cell skips the body)
+  const bool live = t < nc * nc * (nc / KC);
 #pragma unroll 1
   for (int kc = 0; kc < KC; kc++)
-  if (t < nc * nc * (nc / KC)) {
+  if (RS || live) {
     int i, j, kq;
-    cell3(t, nc, i, j, kq);
+    cell3(RS && !live ? 0 : t, nc, i, j, kq);
     const int k = (kq - 1) * KC + 1 + kc;
     const int ng = nc + 2, nf = nc + 1;
     const size_t x = (size_t)(id - 1) * bsz + (size_t)((k * ng + j) * ng + i);
@@ -1391,7 +1460,7 @@ __global__ void __launch_bounds__(256, AFH_UPD_MINW)
         if (ne * dr3 < A.sf.min_e) sfac = 0.0;
       }
       // (add_source_terms returns before this for a wholly masked box)
-      if (A.sf.out && src) A.sf.out[x] = sfac;
+      if (A.sf.out && src && (!RS || live)) A.sf.out[x] = sfac;
     }
     if constexpr (!std::is_void<NET>::value) {
       net_all<NET, SLOW>(A, field, Te, clow, clf, dens, der,
@@ -1406,12 +1475,50 @@ __global__ void __launch_bounds__(256, AFH_UPD_MINW)
         double prod = 1.0;
         for (int q = 0; q < R.n_in; q++) prod = prod * sel(dens, R.ix_in[q] - 1);
         rate = rate * prod;
+        if constexpr (RS) {
+          // chemical_rates_box: sum(rates) of the box's cells; product(dr)
+          // on the workgroup's sum
+          const double ws = wave_sum(live && src ? rate : 0.0);
+          double *slot = rate_sum_lds() + 4 * r + (threadIdx.x >> 6);
+          if ((threadIdx.x & 63) == 0) *slot = kc ? *slot + ws : ws;
+        }
         for (int q = 0; q < R.n_in; q++) add_at(der, R.ix_in[q] - 1, -rate);
         for (int q = 0; q < R.n_out; q++)
           add_at(der, R.ix_out[q] - 1, rate * R.mult_out[q]);
       }
     }
-    if (A.last_step && src) {
+    if constexpr (RS) {
+      // sum_global_JdotE: fc_inner_product(flux_elec, electric_fld) times the
+      // cell volume, in the reference's operand order
+      const double *dr = A.meta ? A.meta[id - 1].dr : A.rs.dr;
+      double e0[3], e1[3];
+      if (A.rs.phi) {
+        const double *ph = A.rs.phi + (size_t)(id - 1) * bsz;
+        const int c0 = (k * ng + j) * ng + i;
+        const int st[3] = {1, ng, ng * ng};
+        const double P0 = ph[c0];
+#pragma unroll
+        for (int d = 0; d < 3; d++) {
+          // fac / dr as the flux kernels take it (k_flux_staged)
+          const double gf = !A.meta ? A.rs.gfac[d]
+                            : A.rs.fac == -1.0 ? -(1 / dr[d]) : A.rs.fac / dr[d];
+          e0[d] = gf * (P0 - ph[c0 - st[d]]);
+          e1[d] = gf * (ph[c0 + st[d]] - P0);
+        }
+      } else {
+        const double *Ef = A.rs.Ef + (size_t)(id - 1) * fsz;
+        e0[0] = Ef[f0], e1[0] = Ef[f0 + 1];
+        e0[1] = Ef[d3 + f0], e1[1] = Ef[d3 + f0 + nf];
+        e0[2] = Ef[2 * d3 + f0], e1[2] = Ef[2 * d3 + f0 + nf * nf];
+      }
+      double ip = 0.5 * (fx0 * e0[0] + fy0 * e0[1] + fz0 * e0[2]);
+      ip = ip + 0.5 * (fx1 * e1[0] + fy1 * e1[1] + fz1 * e1[2]);
+      const double vol = dr[0] * dr[1] * dr[2];
+      const double ws = wave_sum(live && src ? ip * vol : 0.0);
+      double *slot = rate_sum_lds() + 4 * A.nr + (threadIdx.x >> 6);
+      if ((threadIdx.x & 63) == 0) *slot = kc ? *slot + ws : ws;
+    }
+    if (A.last_step && src && (!RS || live)) {
       const double eps = 1e-100;
 #pragma unroll
       for (int s = 0; s < NT; s++) {
@@ -1456,14 +1563,29 @@ __global__ void __launch_bounds__(256, AFH_UPD_MINW)
         if (s == A.ion_s[n]) y[s] = y[s] + ix_ + iy_ + iz_;
     }
 #pragma unroll
-    for (int s = 0; s < NS; s++) st_nt<AFH_NT_UPD>(A.out[s] + x, y[s]);
-    if (A.rhs) {
+    for (int s = 0; s < NS; s++)
+      if (!RS || live) st_nt<AFH_NT_UPD>(A.out[s] + x, y[s]);
+    if (A.rhs && (!RS || live)) {
       double r = 0.0;
 #pragma unroll
       for (int s = 0; s < NS; s++)
         if (A.rq[s] != 0.0) r = r + A.rq[s] * y[s];
       st_nt<AFH_NT_UPD>(A.rhs + x, r);
       rmax = fmax(rmax, fabs(r));
+    }
+  }
+  if constexpr (RS) {
+    // the workgroup's row: the waves' sums in wave order, then product(dr)
+    // on the rates (chemical_rates_box) and UC_elec_charge on J.E
+    __syncthreads();
+    if ((int)threadIdx.x <= A.nr) {
+      const double *w = rate_sum_lds() + 4 * threadIdx.x;
+      double s = w[0];
+      for (int q = 1; q < (int)(blockDim.x >> 6); q++) s = s + w[q];
+      const double *dr = A.meta ? A.meta[id - 1].dr : A.rs.dr;
+      s = (int)threadIdx.x < A.nr ? s * (dr[0] * dr[1] * dr[2]) : s * -1.6022e-19;
+      const size_t row = (size_t)A.rs.row0 + (size_t)blockIdx.y * gridDim.x + blockIdx.x;
+      A.rs.part[row * (A.nr + 1) + threadIdx.x] = s;
     }
   }
   if (A.rhs) block_max_to_shard(rmax, A.rhs_red);
@@ -1513,12 +1635,34 @@ static bool launch_update_net(const UpdArgs &A, afh_tree *t, const dim3 &grid,
 template <int NS>
 void launch_update(const UpdArgs &A, afh_tree *t, int l, int n_boxes,
                    unsigned long long *red, bool slow, int net = 0,
-                   const SrcFacArgs *sf = nullptr) {
+                   const SrcFacArgs *sf = nullptr, const RateSumArgs *rs = nullptr) {
   // boxes leaves.at(l) .. + n_boxes (one level, or every level from 1)
   const int nc = t->nc, n3 = nc * nc * nc;
   const dim3 grid((n3 / AFH_UPD_KC + 255) / 256, n_boxes);
   const auto *ids = t->leaves.at(l);
   const bool sd = A.der_q < 0;
+  if (rs) {
+    // the rate sums of a last step: the generic reaction loop, any previous
+    // states, with or without the source factor
+    auto go = [&](auto B, auto sf_) {
+      constexpr bool SF = decltype(sf_)::value;
+      static_cast<UpdArgs &>(B) = A;
+      if constexpr (SF) B.sf = *sf;
+      B.rs = *rs;
+      if (A.Ng)
+        hipLaunchKernelGGL((k_update<NS, true, MAXPREV, true, true, void, SF, true>), grid,
+                           dim3(256), 0, t->stream, B, ids, nc, t->bsz, t->fsz, red);
+      else if (slow)
+        hipLaunchKernelGGL((k_update<NS, true, MAXPREV, true, false, void, SF, true>), grid,
+                           dim3(256), 0, t->stream, B, ids, nc, t->bsz, t->fsz, red);
+      else
+        hipLaunchKernelGGL((k_update<NS, false, MAXPREV, true, false, void, SF, true>), grid,
+                           dim3(256), 0, t->stream, B, ids, nc, t->bsz, t->fsz, red);
+    };
+    if (sf) go(UpdArgsSfRs{}, std::true_type{});
+    else go(UpdArgsRs{}, std::false_type{});
+    return;
+  }
   if (sf) {
     // the source factor: the generic reaction loop with the per-reaction
     // flags read at run time (no compiled network), any previous states
@@ -2197,6 +2341,12 @@ struct afh_fluid {
   int sf_mode = 0, sf_iv = 0;
   double sf_min_e = 0.0;
   uint8_t *d_sf_ion = nullptr;
+  // afh_fluid_set_rate_sums: on, the workgroups' partial rows (rs_cap rows of
+  // n_reactions + 1 doubles; regrown when the tree has more leaves), the
+  // folded result on the device and whether a last step has filled it
+  bool rs_on = false, rs_valid = false;
+  double *d_rs_part = nullptr, *d_rs_out = nullptr;
+  size_t rs_cap = 0;
   // mobile ions: second ghost layers of each ion [ion][box][6][nc][nc] and
   // the electrons' mu u per face (k_flux_staged -> k_flux_ion)
   double *d_gc2_ion = nullptr, *d_sig = nullptr;
@@ -2363,6 +2513,8 @@ int32_t afh_fluid_destroy(afh_fluid *f) {
   hipFree(f->d_sig);
   hipFree(f->d_mstat);
   hipFree(f->d_sf_ion);
+  hipFree(f->d_rs_part);
+  hipFree(f->d_rs_out);
   delete f;
   return AFH_OK;
 }
@@ -2450,6 +2602,65 @@ int32_t afh_fluid_set_source_factor(afh_fluid *f, int32_t mode, const uint8_t *i
   f->sf_mode = mode;
   f->sf_min_e = min_electrons_per_cell;
   f->sf_iv = i_srcfac;
+  return AFH_OK;
+}
+
+// the partial rows of a last step with the sums on: one per update workgroup
+// of every leaf
+static int32_t rate_sums_reserve(afh_fluid *f) {
+  afh_tree *t = f->t;
+  const int nc = t->nc, n3 = nc * nc * nc;
+  const size_t rows = (size_t)t->leaves.off[t->nlvl] * ((n3 / AFH_UPD_KC + 255) / 256);
+  const size_t ncol = (size_t)f->d.n_reactions + 1;
+  if (!f->d_rs_out) AFH_HIP(hipMalloc(&f->d_rs_out, ncol * sizeof(double)));
+  if (rows > f->rs_cap) {
+    // (a queued fold may still read the old rows)
+    AFH_HIP(hipStreamSynchronize(t->stream));
+    hipFree(f->d_rs_part);
+    f->d_rs_part = nullptr;
+    f->rs_cap = 0;
+    AFH_HIP(hipMalloc(&f->d_rs_part, rows * ncol * sizeof(double)));
+    f->rs_cap = rows;
+  }
+  return AFH_OK;
+}
+
+int32_t afh_fluid_set_rate_sums(afh_fluid *f, int32_t on) {
+  if (!f) return set_error(AFH_ERR_ARG, "afh_fluid_set_rate_sums: null");
+  afh_tree *t = f->t;
+  AFH_LIVE(t, "afh_fluid_set_rate_sums");
+  if (on && (t->hook || t->dev_reduce))
+    return set_error(AFH_ERR_UNSUPPORTED,
+                     "afh_fluid_set_rate_sums: the sums over the ranks of a sharded tree "
+                     "are not built");
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  AFH_HIP(hipStreamIsCapturing(t->stream, &cs));
+  if (cs != hipStreamCaptureStatusNone)
+    return set_error(AFH_ERR_STATE, "afh_fluid_set_rate_sums during a graph capture");
+  if (on && !f->rs_on) {
+    if (int32_t e = rate_sums_reserve(f)) return e;
+    f->rs_valid = false;
+  }
+  f->rs_on = on != 0;
+  return AFH_OK;
+}
+
+int32_t afh_fluid_fetch_rate_sums(afh_fluid *f, double *rates, double *jdote) {
+  if (!f || !jdote || (!rates && f->d.n_reactions > 0))
+    return set_error(AFH_ERR_ARG, "afh_fluid_fetch_rate_sums: null");
+  afh_tree *t = f->t;
+  AFH_LIVE(t, "afh_fluid_fetch_rate_sums");
+  if (!f->rs_on) return set_error(AFH_ERR_STATE, "afh_fluid_fetch_rate_sums: the sums are off");
+  if (!f->rs_valid)
+    return set_error(AFH_ERR_STATE,
+                     "afh_fluid_fetch_rate_sums: no last step since the sums were switched on");
+  const int nr = f->d.n_reactions;
+  double h[AFH_MAX_REACTIONS + 1];
+  AFH_HIP(hipMemcpyAsync(h, f->d_rs_out, (nr + 1) * sizeof(double), hipMemcpyDeviceToHost,
+                         t->stream));
+  AFH_HIP(hipStreamSynchronize(t->stream));
+  for (int r = 0; r < nr; r++) rates[r] = h[r];
+  *jdote = h[nr];
   return AFH_OK;
 }
 
@@ -2966,10 +3177,31 @@ static int32_t update_dev(afh_fluid *f, double dt, int32_t s_deriv, int32_t n_pr
   // dt / dr from each box's meta record: every leaf level in one launch
   const bool all_lvls = t->all_lvl_launch && t->leaves.off[t->nlvl] <= 65535;
   if (all_lvls) A.meta = t->d_boxes;
+  // the rate sums (afh_fluid_set_rate_sums): last steps only
+  const bool rs_on = f->rs_on && last_step;
+  if (rs_on) {
+    if (t->hook || t->dev_reduce)
+      return set_error(AFH_ERR_UNSUPPORTED, "the rate sums on a sharded tree are not built");
+    if ((e = rate_sums_reserve(f))) return e;
+  }
+  const int upd_gx = (n3 / AFH_UPD_KC + 255) / 256;
   for (int l = 1; l <= t->nlvl; l++) {
     const int n = all_lvls ? (l == 1 ? t->leaves.off[t->nlvl] : 0) : t->leaves.n(l);
     if (!n) continue;
     for (int q = 0; q < 3; q++) A.dt_dr[q] = dt / t->lvl_dr[3 * (l - 1) + q];
+    RateSumArgs RS;
+    if (rs_on) {
+      RS.part = f->d_rs_part;
+      RS.row0 = t->leaves.off[l - 1] * upd_gx;
+      RS.Ef = t->fcv(f->d.f_field);
+      RS.phi = f->phi_iv > 0 ? t->ccv(f->phi_iv) : nullptr;
+      RS.fac = f->phi_fac;
+      for (int q = 0; q < 3; q++) {
+        RS.dr[q] = t->lvl_dr[3 * (l - 1) + q];
+        RS.gfac[q] = RS.fac / RS.dr[q];
+      }
+    }
+    const RateSumArgs *rs = rs_on ? &RS : nullptr;
     SrcFacArgs S;
     const bool sf_on = f->sf_mode == AFH_SRCFAC_FLUX;
     if (sf_on) {
@@ -2984,7 +3216,7 @@ static int32_t update_dev(afh_fluid *f, double dt, int32_t s_deriv, int32_t n_pr
     prof_begin(t, AFH_PROF_UPDATE);
     switch (A.ns) {
 #define AFH_CASE(N) \
-  case N: launch_update<N>(A, t, l, n, red, f->slow_rates, f->net, sf); break;
+  case N: launch_update<N>(A, t, l, n, red, f->slow_rates, f->net, sf, rs); break;
       AFH_CASE(1) AFH_CASE(2) AFH_CASE(3) AFH_CASE(4) AFH_CASE(5) AFH_CASE(6)
       AFH_CASE(7) AFH_CASE(8) AFH_CASE(9) AFH_CASE(10) AFH_CASE(11)
       AFH_CASE(12) AFH_CASE(13) AFH_CASE(14) AFH_CASE(15) AFH_CASE(16)
@@ -2992,6 +3224,12 @@ static int32_t update_dev(afh_fluid *f, double dt, int32_t s_deriv, int32_t n_pr
     }
     prof_end(t, AFH_PROF_UPDATE, upd_bytes * n3 * n);
     AFH_LAUNCH_CHECK("k_update");
+  }
+  if (rs_on) {
+    hipLaunchKernelGGL(k_rate_fold, dim3(A.nr + 1), dim3(256), 0, t->stream, f->d_rs_part,
+                       t->leaves.off[t->nlvl] * upd_gx, A.nr + 1, f->d_rs_out);
+    AFH_LAUNCH_CHECK("k_rate_fold");
+    f->rs_valid = true;
   }
   if (A.rhs) {
     // the ghost shell of rhs from the ghost cells of the new state (the
@@ -3165,7 +3403,8 @@ static int32_t fe_dev(afh_fluid *f, double dt, int32_t s_deriv, int32_t n_prev,
                      !f->slow_rates && net_ok && f->d.i_gas_dens <= 0 &&
                      f->d.i_photo <= 0 && n_prev <= 2 && !alias &&
                      f->d.limiter == AFH_LIM_KOREN && f->d.n_ions == 0 && !f->mask_iv &&
-                     f->sf_mode == AFH_SRCFAC_NONE;  // (k_fe_lds has no source factor)
+                     f->sf_mode == AFH_SRCFAC_NONE &&  // (k_fe_lds has no source factor
+                     !(f->rs_on && last_step);          // and forms no rate sums)
   if (!fused) {
     // flux and update back to back on the stream (the flux maxima are not
     // needed before the update); secondary emission from ions at the walls

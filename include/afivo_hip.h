@@ -540,7 +540,9 @@ int32_t afh_fluid_set_update_mask(afh_fluid *f, int32_t i_lsf);
 /* The flux-based source factor of add_source_terms (fixes%source_factor =
  * flux, m_fluid.f90:368-397 and 525-583) is built too; its entry point lies
  * outside this common ABI (the C oracle does not have it) and is declared in
- * afivo_hip_srcfac.h. */
+ * afivo_hip_srcfac.h. So are the space integrals of the reaction rates and of
+ * J.E over a last step (chemical_rates_box, sum_global_JdotE, m_fluid.f90:
+ * 665-731): afivo_hip_rates.h. */
 /* flux_update_densities with add_source_terms / set_box_mask
  * (m_af_flux_schemes.f90:320-436, src/m_fluid.f90:298-515); dt_lim[2] =
  * (chemistry limit on the last step, 1e100 otherwise; energy limit). */

@@ -47,7 +47,9 @@
  * in the update), and the flux-based source factor of the species update
  * (fixes%source_factor = flux; its entry point is declared in
  * afivo_hip_srcfac.h, outside the common ABI, and combines with cylindrical
- * coordinates, photoionization, the update mask and mobile ions). Not built in 2-D
+ * coordinates, photoionization, the update mask and mobile ions), and the
+ * rate and J.E sums of a last step (afivo_hip_rates.h, likewise outside the
+ * common ABI; with af_cyl_volume_cc on a cylindrical tree). Not built in 2-D
  * (AFH_ERR_UNSUPPORTED or not exported): electrodes in cylindrical
  * coordinates, variable
  * gas density, the temperature rate forms, sharding, ion
