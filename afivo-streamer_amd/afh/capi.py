@@ -230,7 +230,15 @@ SIGNATURES_RATES = {
     "fluid_set_rate_sums": (i32, [_VP, i32]),
     "fluid_fetch_rate_sums": (i32, [_VP, P_f64, P_f64]),
 }
-SIGNATURES_EXTRA = dict(SIGNATURES_SRCFAC, **SIGNATURES_RATES)
+# the reductions behind the simulation log and the field maxima
+# (include/afivo_hip_analysis.h): both HIP libraries, not the oracle
+SIGNATURES_ANALYSIS = {
+    "tree_reduce_fc": (i32, [_VP, i32, i32, i32, P_f64, P_i32]),
+    "tree_zminmax_threshold": (i32, [_VP, i32, f64, P_f64, P_f64]),
+    "tree_max_region": (i32, [_VP, i32, P_f64, P_f64, P_f64, P_i32]),
+    "tree_local_maxima": (i32, [_VP, i32, f64, i32, P_f64, P_i32]),
+}
+SIGNATURES_EXTRA = dict(SIGNATURES_SRCFAC, **SIGNATURES_RATES, **SIGNATURES_ANALYSIS)
 DIST_LOCAL, DIST_RCCL = 1, 2
 HOOK_HALO, HOOK_RIMS, HOOK_RESTRICT, HOOK_MAX, HOOK_MIN, HOOK_CFLUX = 1, 2, 3, 4, 5, 6
 HOOK_SUM = 7

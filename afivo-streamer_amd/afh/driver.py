@@ -26,6 +26,7 @@ af_bc_neumann_zero, photoi_helmh_bc, default_refinement).
 """
 import math
 import os
+import time
 
 import numpy as np
 
@@ -123,10 +124,16 @@ class Simulation:
 
     def __init__(self, lib, case, device=-1, coarse_cycles=0, capacity_factor=2.0,
                  fuse_rhs=True, user=None, coarse_tol=0.0, coarse_mode=None,
-                 global_rates=False):
+                 global_rates=False, log=False):
         """global_rates: keep ST_global_rates, ST_global_JdotE and Sato's
         currents (streamer.f90:290-317) from the sums of every accepted
         step's last sub-step (include/afivo_hip_rates.h); diagnostics().
+        log: keep the simulation log (output_log, m_output.f90:496-670): one
+        row per output in sim_log, from the device reductions of
+        include/afivo_hip_analysis.h; log_row(), write_log(). It implies
+        global_rates (the row prints ST_global_JdotE and the currents). With
+        the case entry field_maxima%write each output also keeps
+        output_fld_maxima's list; field_maxima(), write_field_maxima().
         user: the program's m_user hooks (afh.users), e.g. the gas density
         function and initial conditions of programs/3d_sprite.
         coarse_cycles / coarse_tol: the level-1 solve (0: exact; else at most
@@ -318,10 +325,31 @@ class Simulation:
                     raise ValueError("write_source_factor: no cc variable named srcfac "
                                      "in cc_names")
                 self.i_srcfac = self.cc_names.index("srcfac") + 1
+        # the simulation log and the field maxima (m_output.f90:496-670,
+        # 869-912). output%density_threshold and the three field_maxima%
+        # entries are optional in the case dict (the exporter does not write
+        # them), else the reference's defaults (m_output.f90:79-85, 94)
+        self.log_on = bool(log)
+        self.sim_log = []
+        self.log_prev_pos = None  # output_log's saved prev_pos; not in the .dat record
+        self.dt_limits = [0.0] * 4  # m_dt's dt_limits: cfl, drt, chem, other
+        self.density_threshold = c.r("output%density_threshold") \
+            if "output%density_threshold" in c.d else 1e18
+        self.field_maxima_write = bool(c.i("field_maxima%write")) \
+            if "field_maxima%write" in c.d else False
+        self.field_maxima_threshold = c.r("field_maxima%threshold") \
+            if "field_maxima%threshold" in c.d else 0.0
+        self.field_maxima_distance = c.r("field_maxima%distance") \
+            if "field_maxima%distance" in c.d else 0.0
+        self.fld_maxima = None
+        if (self.log_on or self.field_maxima_write) and not lib.has("tree_local_maxima"):
+            raise NotImplementedError(
+                "log / field_maxima%write: the reductions of the simulation log are not "
+                "built in this library (include/afivo_hip_analysis.h: the HIP libraries)")
         # ST_global_rates, ST_global_JdotE and the currents of Sato's equation
         # (streamer.f90:290-317); current_update_per_steps: optional in the
         # case dict, else the reference's default (m_streamer.f90:169)
-        self.rate_sums = bool(global_rates)
+        self.rate_sums = bool(global_rates) or self.log_on
         if self.rate_sums and not lib.has("fluid_set_rate_sums"):
             raise NotImplementedError(
                 "global_rates: the rate and J.E sums are not built in this library "
@@ -352,6 +380,7 @@ class Simulation:
         self.frac_rejected = 0.0
         self.output_cnt = 0
         self.log = []
+        self._wc_start = time.time()  # (start() and restart() set it again)
         # mesh: af_init (streamer.f90:151-153)
         nc = c.i("box_size")
         # periodic (m_streamer.f90:362, af_init's argument in streamer.f90:152):
@@ -919,6 +948,7 @@ class Simulation:
         lim = self.fluid.forward_euler(dt, s_deriv, s_prev, w_prev, s_out,
                                        i_step == n_steps)
         limits = [lim[0] * self.cfl, lim[1], lim[2], lim[3]]
+        self.dt_limits = limits
         return min(self.dt_max, min(limits))
 
     def advance(self, dt):
@@ -1141,6 +1171,116 @@ class Simulation:
                 self.tree.restrict_tree(iv)
                 self.tree.gc_tree(iv)
         self.log.append(self.regression_row())
+        if self.log_on:
+            self.sim_log.append(self.log_row(advance=True)[1])
+        if self.field_maxima_write:
+            self.fld_maxima = self._fld_maxima()
+
+    # ------------------------------------------------------ simulation log
+    def _r_loc(self, loc):
+        """af_r_loc: r_min + (ix - 0.5) dr of the located box (a face
+        location too)."""
+        b = loc[0]
+        return [float(self.af.r_min[b][d] + (loc[1 + d] - 0.5) * self.af.dr[b][d])
+                for d in range(self.ndim)]
+
+    def log_row(self, advance=False):
+        """The columns of output_log (m_output.f90:532-581, 632-666) for the
+        current state: (dict by column name, the ordered list simlog.format_row
+        takes). The extrema, the plasma's extent and the tip field are device
+        reductions (include/afivo_hip_analysis.h); no cell changes. The
+        velocity is measured from the position of max(E) at the previous row
+        of the run (advance=True, as run() calls it, moves that position on);
+        the first row of a run, and of a restarted one, has v = 0."""
+        from . import simlog
+        if not self.log_on:
+            raise RuntimeError("log_row: the run was created without log=True")
+        t, nd, c = self.tree, self.ndim, self.c
+        sum_elec = t.sum_cc(self.i_electron, 1)
+        sum_pos_ion = t.sum_cc(self.i_1pos_ion, 1)
+        max_elec, loc_elec = t.reduce_loc(self.i_electron, capi.RED_MAX)
+        max_field, loc_field = t.reduce_loc(self.i_efld, capi.RED_MAX)
+        if nd == 2:
+            if self.faces_from_phi:  # the face field is not kept: form it
+                self.mg.compute_phi_gradient(self.f_field, -1.0, 0)
+            max_Er, loc_Er = t.reduce_fc(self.f_field, 1, capi.RED_MAX)
+            min_Er = t.reduce_fc(self.f_field, 1, capi.RED_MIN, with_loc=False)[0]
+        # the threshold scales with the gas number density
+        threshold = self.density_threshold * (self.N / 2.414e25) ** 2
+        L, o = self.L, self.origin
+        z = t.zminmax_threshold(self.i_electron, threshold, [L[nd - 1], 0.0])
+        # the tip: the plasma's end farthest from the electrode boundaries
+        r0 = np.array(o, float)
+        r1 = np.array(o, float) + np.array(L, float)
+        k = nd - 1
+        if z[0] - o[k] < o[k] + L[k] - z[1]:
+            r0[k] = z[1] - 0.02 * L[k]
+            r1[k] = z[1] + 0.02 * L[k]
+        else:
+            r0[k] = z[0] - 0.02 * L[k]
+            r1[k] = z[0] + 0.02 * L[k]
+        max_field_tip, loc_tip = t.max_region(self.i_efld, r0, r1)
+        r_tip = self._r_loc(loc_tip) if loc_tip[0] > 0 else [0.0] * nd
+        sum_elem_charge = 0.0
+        for n in range(self.n_gas, len(self.species_list)):
+            if self.species_charge[n] != 0 and self.species_itree[n] > 0:
+                tmp = t.sum_cc(self.species_itree[n], 1)
+                sum_elem_charge = sum_elem_charge + tmp * self.species_charge[n]
+        pos = self._r_loc(loc_field)
+        prev = pos if self.log_prev_pos is None else self.log_prev_pos
+        velocity = _norm2(np.array(pos) - np.array(prev)) / c.r("output%dt")
+        if advance:
+            self.log_prev_pos = pos
+        wc_time = time.time() - self._wc_start
+        d = {"it": self.output_cnt, "time": self.global_time, "dt": self.global_dt,
+             "v": velocity, "sum(n_e)": sum_elec, "sum(n_i)": sum_pos_ion,
+             "sum(charge)": sum_elem_charge, "sum(J.E)": self.global_JdotE,
+             "max(E)": max_field, "r(E)": pos, "max(n_e)": max_elec,
+             "r(n_e)": self._r_loc(loc_elec)}
+        if nd == 2:
+            d.update({"max(E_r)": max_Er, "r(E_r)": self._r_loc(loc_Er), "min(E_r)": min_Er})
+        d.update({"voltage": self.voltage, "current_J.E": self.JdotE_current,
+                  "current_displ": self.displ_current, "ne_zmin": z[0], "ne_zmax": z[1],
+                  "max(Etip)": max_field_tip, "r(Etip)": r_tip, "wc_time": wc_time,
+                  "n_cells": self.af.n_leaf_cells(), "min(dx)": self.af.min_dr(),
+                  "dt_limits": list(self.dt_limits), "highest(lvl)": self.af.highest_lvl})
+        row = []
+        for v in d.values():
+            row.extend(v if isinstance(v, list) else [v])
+        assert len(row) == simlog.N_REALS[nd] + 8
+        return d, row
+
+    def write_log(self, path):
+        """<name>_log.txt: the header of m_output.f90:586-611 and the rows of
+        sim_log in (I6,<n>E20.8e3,I12,5E20.8e3,I3)."""
+        from . import simlog
+        with open(path, "w") as f:
+            f.write(simlog.header_line(self.ndim))
+            for row in self.sim_log:
+                f.write(simlog.format_row(self.ndim, row) + "\n")
+
+    def _fld_maxima(self):
+        """output_fld_maxima (m_output.f90:869-912) up to its write: the
+        local maxima of |E| (n_max = 1000; its ghost cells filled first),
+        merged where closer than field_maxima%distance."""
+        from . import simlog
+        self.tree.gc_tree(self.i_efld)
+        cv, n_found = self.tree.local_maxima(self.i_efld, self.field_maxima_threshold, 1000)
+        return simlog.merge_maxima(cv, n_found, self.field_maxima_distance,
+                                   self.field_maxima_threshold)
+
+    def field_maxima(self):
+        """The merged list of the most recent output, (n, NDIM + 1): the
+        coordinates, then |E|."""
+        if not self.field_maxima_write:
+            raise RuntimeError("field_maxima: the case has no field_maxima%write")
+        return self._fld_maxima() if self.fld_maxima is None else self.fld_maxima.copy()
+
+    def write_field_maxima(self, path):
+        """<name>_Emax_<cnt>.txt: one row per maximum of field_maxima()."""
+        with open(path, "w") as f:
+            for r in self.field_maxima():
+                f.write(" ".join("%25.16E" % x for x in r) + "\n")
 
     # --------------------------------------------------------------- run
     def step(self):
@@ -1336,9 +1476,14 @@ class Simulation:
         self.dt = self.global_dt
         self.time_last_output = self.time  # streamer.f90:172
         self._field_energy_start()
+        # (output_log's prev_pos is a saved variable, not part of the record:
+        # the first row after a restart has v = 0)
+        self.log_prev_pos = None
+        self._wc_start = time.time()
         return t
 
     def start(self):
+        self._wc_start = time.time()
         self.set_initial_conditions()
         self.output_cnt = 0
         self.output_write()

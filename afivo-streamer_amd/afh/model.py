@@ -344,6 +344,49 @@ class Tree:
     def min_cc(self, iv):
         return self.reduce_loc(iv, capi.RED_MIN, with_loc=False)[0]
 
+    # -- the reductions of include/afivo_hip_analysis.h (the HIP libraries)
+    def reduce_fc(self, ivf, dim, op, with_loc=True):
+        """af_tree_max_fc / af_tree_min_fc (op = capi.RED_MAX / RED_MIN) of
+        fc(.., dim, ivf), dim 1-based, the upper-boundary faces included:
+        (value, (id, i, j, k)) with the face index, nc + 1 at most along dim."""
+        out = C.c_double()
+        loc = np.zeros(4, np.int32)
+        self.lib.call("tree_reduce_fc", self.h, ivf, int(dim), int(op), C.byref(out),
+                      loc.ctypes.data_as(capi.P_i32) if with_loc else None)
+        return out.value, (tuple(int(x) for x in loc) if with_loc else None)
+
+    def zminmax_threshold(self, iv, threshold, limits):
+        """analysis_zmin_zmax_threshold as written (a leaf's zmax entry is its
+        first plane above the threshold): (zmin, zmax) folded from limits."""
+        lim = np.array(limits, np.float64)
+        out = np.zeros(2)
+        self.lib.call("tree_zminmax_threshold", self.h, iv, float(threshold),
+                      lim.ctypes.data_as(capi.P_f64), out.ctypes.data_as(capi.P_f64))
+        return float(out[0]), float(out[1])
+
+    def max_region(self, iv, r0, r1, with_loc=True):
+        """analysis_max_var_region over the leaves that touch r0 .. r1:
+        (value, (id, i, j, k)), or (-1e100, (-1, ...)) when none does."""
+        a0, a1 = np.zeros(3), np.zeros(3)
+        a0[:self.ndim], a1[:self.ndim] = r0, r1
+        out = C.c_double()
+        loc = np.zeros(4, np.int32)
+        self.lib.call("tree_max_region", self.h, iv, a0.ctypes.data_as(capi.P_f64),
+                      a1.ctypes.data_as(capi.P_f64), C.byref(out),
+                      loc.ctypes.data_as(capi.P_i32) if with_loc else None)
+        return out.value, (tuple(int(x) for x in loc) if with_loc else None)
+
+    def local_maxima(self, iv, threshold, n_max=1000):
+        """analysis_get_maxima: (coord_val, n_found) with coord_val the
+        stored maxima, (min(n_found, n_max), ndim + 1) -- coordinates, then
+        the value -- ordered by leaf, then cell. The ghost cells of iv are
+        read as they stand (gc_tree first)."""
+        cv = np.zeros((max(int(n_max), 1), self.ndim + 1))
+        n = C.c_int32()
+        self.lib.call("tree_local_maxima", self.h, iv, float(threshold), int(n_max),
+                      cv.ctypes.data_as(capi.P_f64), C.byref(n))
+        return cv[:min(n.value, int(n_max))].copy(), n.value
+
 
 class Multigrid:
     """mg_t bound to a tree (mg_init / mg_fas_vcycle)."""

@@ -110,8 +110,10 @@
 #include "../../include/afivo_hip_2d.h"
 #include "../../include/afivo_hip_srcfac.h"
 #include "../../include/afivo_hip_rates.h"
+#include "../../include/afivo_hip_analysis.h"
 #include "afh_cs_tables.h"
 #include "afh_pfmg_dev.h"
+#include "afh_analysis_dev.h"
 
 namespace afh2 {
 
@@ -2116,6 +2118,10 @@ struct afh_tree {
   std::vector<double> lvl_dr;  // 2 per level
   double *d_boxred = nullptr;  // per-leaf (value, cell) of afh_tree_sum_cc / reduce_loc
   uint8_t *d_leaf = nullptr;   // per box id: a leaf (k2_photoi_sum; made on first use)
+  // results of the afivo_hip_analysis.h reductions on the device (an_cap
+  // doubles): 4 for a value and its place, then the list of local maxima
+  double *d_an = nullptr;
+  size_t an_cap = 0;
   // kernel timing (afh_profile_enable/read, as in libafivo_hip): HIP events
   // around every launch of one kernel class on the tree's stream
   int prof_class = 0;
@@ -2484,6 +2490,7 @@ int32_t afh_tree_destroy(afh_tree *t) {
     free_list(*L);
   hipFree(t->d_boxes), hipFree(t->cc), hipFree(t->fc), hipFree(t->gc2);
   hipFree(t->red), hipFree(t->red_out), hipHostFree(t->h_red), hipFree(t->d_boxred);
+  hipFree(t->d_an);
   hipFree(t->d_leaf);
   for (hipEvent_t e : t->ev_pool) hipEventDestroy(e);
   hipStreamDestroy(t->stream);
@@ -4606,6 +4613,85 @@ int32_t afh_refine_flags(afh_fluid *f, const afh_refine_desc *d, const uint8_t *
   H2(hipMemcpyAsync(masks, d_masks, sizeof(uint32_t) * nb, hipMemcpyDeviceToHost, t->stream));
   H2(hipStreamSynchronize(t->stream));
   hipFree(d_flags), hipFree(d_masks), hipFree(d_elec);
+  return AFH_OK;
+}
+
+// The reductions of afivo_hip_analysis.h (kernels and launchers:
+// afh_analysis_dev.h) with the 2-D shapes: loc = (id, i, j, 0), r0 and r1 read
+// to their second entry, coord_val 3 x n_max. (No tree of this library is
+// sharded.) The launchers' view of the tree, with the per-leaf scratch and the
+// result buffer (4 + n_list doubles) grown to fit.
+#define AN2_TREE(t, what) \
+  if (!(t)) return set_error(AFH_ERR_ARG, "%s: null tree", what)
+static int32_t an_ctx(afh_tree *t, size_t n_list, const char *what, afh_an::Ctx &c) {
+  const int nl = t->leaves.off[t->nlvl];
+  if (!t->d_boxred) H2(hipMalloc(&t->d_boxred, sizeof(double) * 2 * t->nb));
+  if (4 + n_list > t->an_cap) {
+    H2(hipStreamSynchronize(t->stream));
+    hipFree(t->d_an);
+    t->d_an = nullptr, t->an_cap = 0;
+    H2(hipMalloc(&t->d_an, sizeof(double) * (4 + n_list)));
+    t->an_cap = 4 + n_list;
+  }
+  c.stream = t->stream;
+  c.nd = 2, c.nc = t->nc, c.nl = nl;
+  c.leaves = t->leaves.d;
+  c.meta = t->d_boxes;
+  c.part = t->d_boxred, c.res = t->d_an;
+  return AFH_OK;
+}
+
+int32_t afh_tree_reduce_fc(afh_tree *t, int32_t ivf, int32_t dim, int32_t op, double *out,
+                           int32_t *loc) {
+  AN2_TREE(t, "afh_tree_reduce_fc");
+  if (ivf < 1 || ivf > t->nvf || dim < 1 || dim > 2 || !out ||
+      (op != AFH_RED_MAX && op != AFH_RED_MIN))
+    return set_error(AFH_ERR_ARG, "afh_tree_reduce_fc: bad argument");
+  afh_an::Ctx c;
+  if (int32_t e = an_ctx(t, 0, "afh_tree_reduce_fc", c)) return e;
+  const bool is_min = op == AFH_RED_MIN;
+  afh_an::Region none = {};
+  H2(afh_an::best_loc(c, t->fcv(ivf), afh_an::geo_fc(2, t->nc, t->fsz, dim - 1), is_min,
+                           none, (is_min ? 1 : -1) * (1.7976931348623157e308 / 10), out, loc));
+  return AFH_OK;
+}
+
+int32_t afh_tree_zminmax_threshold(afh_tree *t, int32_t iv, double threshold,
+                                   const double *limits, double *out) {
+  AN2_TREE(t, "afh_tree_zminmax_threshold");
+  if (iv < 1 || iv > t->nvc || !limits || !out)
+    return set_error(AFH_ERR_ARG, "afh_tree_zminmax_threshold: bad argument");
+  afh_an::Ctx c;
+  if (int32_t e = an_ctx(t, 0, "afh_tree_zminmax_threshold", c)) return e;
+  H2(afh_an::zminmax(c, t->ccv(iv), afh_an::geo_cc(2, t->nc, t->bsz), threshold, limits,
+                          out));
+  return AFH_OK;
+}
+
+int32_t afh_tree_max_region(afh_tree *t, int32_t iv, const double *r0, const double *r1,
+                            double *out, int32_t *loc) {
+  AN2_TREE(t, "afh_tree_max_region");
+  if (iv < 1 || iv > t->nvc || !r0 || !r1 || !out)
+    return set_error(AFH_ERR_ARG, "afh_tree_max_region: bad argument");
+  afh_an::Ctx c;
+  if (int32_t e = an_ctx(t, 0, "afh_tree_max_region", c)) return e;
+  afh_an::Region R = {};
+  R.on = 1;
+  for (int d = 0; d < 2; d++) R.r0[d] = r0[d], R.r1[d] = r1[d];
+  H2(afh_an::best_loc(c, t->ccv(iv), afh_an::geo_cc(2, t->nc, t->bsz), false, R, -1e100,
+                           out, loc));
+  return AFH_OK;
+}
+
+int32_t afh_tree_local_maxima(afh_tree *t, int32_t iv, double threshold, int32_t n_max,
+                              double *coord_val, int32_t *n_found) {
+  AN2_TREE(t, "afh_tree_local_maxima");
+  if (iv < 1 || iv > t->nvc || n_max < 0 || (n_max > 0 && !coord_val) || !n_found)
+    return set_error(AFH_ERR_ARG, "afh_tree_local_maxima: bad argument");
+  afh_an::Ctx c;
+  if (int32_t e = an_ctx(t, (size_t)3 * n_max, "afh_tree_local_maxima", c)) return e;
+  H2(afh_an::maxima(c, t->ccv(iv), afh_an::geo_cc(2, t->nc, t->bsz), threshold, n_max,
+                         coord_val, n_found));
   return AFH_OK;
 }
 

@@ -181,6 +181,10 @@ struct afh_tree {
   // per-box partial results of afh_tree_sum_cc / afh_tree_reduce_loc
   double *d_boxred = nullptr;
   int boxred_cap = 0;
+  // results of the afivo_hip_analysis.h reductions on the device (an_cap
+  // doubles): 4 for a value and its place, then the list of local maxima
+  double *d_an = nullptr;
+  size_t an_cap = 0;
   // sharded tree: boxes whose leaf sum another rank contributes (the
   // replicated levels below the partition level count on rank 0 only);
   // empty on an unsharded tree

@@ -17,6 +17,8 @@
 #include <cmath>
 
 #include "afh_internal.h"
+#include "../../include/afivo_hip_analysis.h"
+#include "afh_analysis_dev.h"
 
 namespace afh {
 
@@ -1050,6 +1052,7 @@ int32_t afh_tree_destroy(afh_tree *t) {
   for (hipEvent_t &q : t->side_ev)
     if (q) hipEventDestroy(q);
   hipFree(t->d_boxred);
+  hipFree(t->d_an);
   hipHostFree(t->h_scratch);
   if (t->own_stream) hipStreamDestroy(t->stream);
   delete t;
@@ -1413,6 +1416,90 @@ int32_t afh_tree_reduce_loc(afh_tree *t, int32_t iv, int32_t op, double *out,
     loc[3] = lix < 0 ? -1 : lix / (nc * nc) + 1;
   }
   return call_hook(t, is_min ? AFH_HOOK_MIN : AFH_HOOK_MAX, 0, iv, out, 1);
+}
+
+// The reductions of afivo_hip_analysis.h (kernels and launchers:
+// afh_analysis_dev.h). The launchers' view of the tree, with the per-leaf
+// scratch and the result buffer (4 + n_list doubles) grown to fit.
+static int32_t an_ctx(afh_tree *t, size_t n_list, const char *what, afh_an::Ctx &c) {
+  if (t->hook || t->dev_reduce)
+    return set_error(AFH_ERR_UNSUPPORTED, "%s: the fold over the ranks of a sharded tree is "
+                     "not built", what);
+  const int nl = t->leaves.off[t->nlvl];
+  if (nl > t->boxred_cap) {
+    AFH_HIP(hipStreamSynchronize(t->stream));
+    hipFree(t->d_boxred);
+    t->d_boxred = nullptr, t->boxred_cap = 0;
+    AFH_HIP(hipMalloc(&t->d_boxred, sizeof(double) * 2 * nl));
+    t->boxred_cap = nl;
+  }
+  if (4 + n_list > t->an_cap) {
+    AFH_HIP(hipStreamSynchronize(t->stream));
+    hipFree(t->d_an);
+    t->d_an = nullptr, t->an_cap = 0;
+    AFH_HIP(hipMalloc(&t->d_an, sizeof(double) * (4 + n_list)));
+    t->an_cap = 4 + n_list;
+  }
+  c.stream = t->stream;
+  c.nd = 3, c.nc = t->nc, c.nl = nl;
+  c.leaves = t->leaves.d;
+  c.meta = t->d_boxes;
+  c.part = t->d_boxred, c.res = t->d_an;
+  return AFH_OK;
+}
+
+int32_t afh_tree_reduce_fc(afh_tree *t, int32_t ivf, int32_t dim, int32_t op, double *out,
+                           int32_t *loc) {
+  AFH_LIVE(t, "afh_tree_reduce_fc");
+  if (ivf < 1 || ivf > t->nvf || dim < 1 || dim > 3 || !out ||
+      (op != AFH_RED_MAX && op != AFH_RED_MIN))
+    return set_error(AFH_ERR_ARG, "afh_tree_reduce_fc: bad argument");
+  afh_an::Ctx c;
+  if (int32_t e = an_ctx(t, 0, "afh_tree_reduce_fc", c)) return e;
+  const bool is_min = op == AFH_RED_MIN;
+  afh_an::Region none = {};
+  AFH_HIP(afh_an::best_loc(c, t->fcv(ivf), afh_an::geo_fc(3, t->nc, t->fsz, dim - 1), is_min,
+                           none, (is_min ? 1 : -1) * (DBL_MAX / 10), out, loc));
+  return AFH_OK;
+}
+
+int32_t afh_tree_zminmax_threshold(afh_tree *t, int32_t iv, double threshold,
+                                   const double *limits, double *out) {
+  AFH_LIVE(t, "afh_tree_zminmax_threshold");
+  if (iv < 1 || iv > t->nvc || !limits || !out)
+    return set_error(AFH_ERR_ARG, "afh_tree_zminmax_threshold: bad argument");
+  afh_an::Ctx c;
+  if (int32_t e = an_ctx(t, 0, "afh_tree_zminmax_threshold", c)) return e;
+  AFH_HIP(afh_an::zminmax(c, t->ccv(iv), afh_an::geo_cc(3, t->nc, t->bsz), threshold, limits,
+                          out));
+  return AFH_OK;
+}
+
+int32_t afh_tree_max_region(afh_tree *t, int32_t iv, const double *r0, const double *r1,
+                            double *out, int32_t *loc) {
+  AFH_LIVE(t, "afh_tree_max_region");
+  if (iv < 1 || iv > t->nvc || !r0 || !r1 || !out)
+    return set_error(AFH_ERR_ARG, "afh_tree_max_region: bad argument");
+  afh_an::Ctx c;
+  if (int32_t e = an_ctx(t, 0, "afh_tree_max_region", c)) return e;
+  afh_an::Region R = {};
+  R.on = 1;
+  for (int d = 0; d < 3; d++) R.r0[d] = r0[d], R.r1[d] = r1[d];
+  AFH_HIP(afh_an::best_loc(c, t->ccv(iv), afh_an::geo_cc(3, t->nc, t->bsz), false, R, -1e100,
+                           out, loc));
+  return AFH_OK;
+}
+
+int32_t afh_tree_local_maxima(afh_tree *t, int32_t iv, double threshold, int32_t n_max,
+                              double *coord_val, int32_t *n_found) {
+  AFH_LIVE(t, "afh_tree_local_maxima");
+  if (iv < 1 || iv > t->nvc || n_max < 0 || (n_max > 0 && !coord_val) || !n_found)
+    return set_error(AFH_ERR_ARG, "afh_tree_local_maxima: bad argument");
+  afh_an::Ctx c;
+  if (int32_t e = an_ctx(t, (size_t)4 * n_max, "afh_tree_local_maxima", c)) return e;
+  AFH_HIP(afh_an::maxima(c, t->ccv(iv), afh_an::geo_cc(3, t->nc, t->bsz), threshold, n_max,
+                         coord_val, n_found));
+  return AFH_OK;
 }
 
 int32_t afh_tree_fetch_reduced(afh_tree *t, int32_t n, const int32_t *slots, double *out) {

@@ -368,6 +368,10 @@ int32_t afh_tree_sum_cc(afh_tree *t, int32_t iv, int32_t power, double *out);
 #define AFH_RED_MAXABS 3
 int32_t afh_tree_reduce_loc(afh_tree *t, int32_t iv, int32_t op, double *out,
                             int32_t *loc);
+/* The other reductions of output_log and output_fld_maxima (src/m_output.f90:
+ * 496-670, 869-912) -- a face variable's extremum, the extent above a
+ * threshold, the maximum over a region, the local maxima -- lie outside this
+ * common ABI (the C oracle does not have them): afivo_hip_analysis.h. */
 
 /* mg_init (m_af_multigrid.f90:43-109) + stencils; mg_fas_vcycle (185-264) */
 int32_t afh_mg_create(afh_tree *t, const afh_mg_desc *desc, afh_mg **out);

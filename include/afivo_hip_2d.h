@@ -102,6 +102,14 @@
 #include "afivo_hip.h"
 /* the entry points only the 2-D library has (cylindrical coordinates) */
 #include "afivo_hip_2d_cyl.h"
+/* the reductions behind the simulation log and the field maxima, outside the
+ * common ABI like afivo_hip_rates.h. With the 2-D shapes: a location is
+ * (id, i, j, 0) -- where there is none, (-1, -1, -1, 0) --, the face
+ * reduction takes dim = 1 or 2 over fc(1:nc+1, 1:nc, 1, ivf) or
+ * fc(1:nc, 1:nc+1, 2, ivf), the threshold extent runs along the second
+ * dimension (z of a cylindrical tree), r0 and r1 of the region are read to
+ * their second entry, and coord_val of the local maxima is 3 x n_max. */
+#include "afivo_hip_analysis.h"
 
 #ifdef __cplusplus
 extern "C" {
