@@ -5,6 +5,10 @@
 // 2-D conventions there: a box holds box%cc(0:nc+1, 0:nc+1, iv) (i fastest),
 // box%fc(1:nc+1, 1:nc+1, 1:2, ivf), the first 4 / 4 / 9 / 2 entries of
 // afh_box_meta's children / neighbors / neighbor_mat / ix, r_min, dr.
+// What does not depend on the dimension (error text, AFH_HIP, level lists,
+// kernel timing, limiter, lookup tables, reactions and the field rate forms,
+// NORM2, ordered keys, the rate-sum folds, the bodies of the feature entry
+// points) is in afh_common.h and afh_analysis_dev.h, shared with libafivo_hip.
 //
 // Device layout (HBM): cc pool [iv][box][j][i], (nc+2)^2 doubles per box;
 // fc pool [ivf][box][dim][j][i], (nc+1)^2 per dim; gc2 (second ghost layer
@@ -102,6 +106,7 @@
 
 #include <algorithm>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <type_traits>
@@ -111,38 +116,14 @@
 #include "../../include/afivo_hip_srcfac.h"
 #include "../../include/afivo_hip_rates.h"
 #include "../../include/afivo_hip_analysis.h"
+#include "afh_common.h"
 #include "afh_cs_tables.h"
 #include "afh_pfmg_dev.h"
 #include "afh_analysis_dev.h"
 
 namespace afh2 {
 
-static thread_local std::string g_err;
-
-int32_t set_error(int32_t code, const char *fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  g_err = buf;
-  return code;
-}
-
-int32_t check_hip(hipError_t e, const char *what) {
-  return set_error(AFH_ERR_DEVICE, "%s: %s", what, hipGetErrorString(e));
-}
-
-#define H2(call)                                                              \
-  do {                                                                        \
-    hipError_t _e = (call);                                                   \
-    if (_e != hipSuccess) return ::afh2::check_hip(_e, #call);                \
-  } while (0)
-#define H2_LAUNCH(what)                                                       \
-  do {                                                                        \
-    hipError_t _e = hipGetLastError();                                        \
-    if (_e != hipSuccess) return ::afh2::check_hip(_e, what);                 \
-  } while (0)
+using namespace afhc;
 
 constexpr int NT = 256;          // threads per workgroup
 constexpr int AFH2_MAX_N_CELL = 1024;  // afh_tree_create (afivo_hip_2d.h)
@@ -155,21 +136,6 @@ constexpr int CS2_CELLS = 4096;  // level-1 grids the one-workgroup solve holds
 // ------------------------------------------------------------ device helpers
 __device__ __forceinline__ int red_shard() {
   return (int)((blockIdx.x + gridDim.x * blockIdx.y) & (RED_SHARDS - 1));
-}
-__device__ __forceinline__ unsigned long long dbl_to_ord(double x) {
-  unsigned long long u = __double_as_longlong(x);
-  return (u & 0x8000000000000000ull) ? ~u : (u | 0x8000000000000000ull);
-}
-inline double ord_to_dbl(unsigned long long o) {
-  unsigned long long u = (o & 0x8000000000000000ull) ? (o & ~0x8000000000000000ull) : ~o;
-  double d;
-  memcpy(&d, &u, sizeof d);
-  return d;
-}
-inline unsigned long long host_ord(double x) {
-  unsigned long long u;
-  memcpy(&u, &x, sizeof u);
-  return (u & 0x8000000000000000ull) ? ~u : (u | 0x8000000000000000ull);
 }
 // fold a per-thread max (MAXV) or min into shard red_shard() of `red`; every
 // thread of the (NT-thread) workgroup calls
@@ -195,37 +161,6 @@ __device__ __forceinline__ void block_fold(double v, unsigned long long *red) {
 }
 
 __device__ __forceinline__ int ix2(int ng, int i, int j) { return j * ng + i; }
-
-// af_limiter_apply (m_af_limiters.f90:41-149)
-__device__ __forceinline__ double limiter(int lim, double a, double b) {
-  const double third = 1 / 3.0;
-  switch (lim) {
-  case AFH_LIM_KOREN: {
-    const double aa = a * a, ab = a * b;
-    if (ab <= 0) return 0;
-    if (aa <= 0.25 * ab) return 2 * a;
-    if (aa <= 2.5 * ab) return third * (b + 2 * a);
-    return 2 * b;
-  }
-  case AFH_LIM_VANLEER: {
-    const double ab = a * b;
-    return ab > 0 ? 2 * ab / (a + b) : 0;
-  }
-  case AFH_LIM_NONE: return 0.5 * (a + b);
-  case AFH_LIM_ZERO: return 0.0;
-  default: {
-    const double th = lim == AFH_LIM_MINMOD ? 1.0 : lim == AFH_LIM_MC ? 2.0 : 4 / 3.0;
-    if (a * b > 0) {
-      double m = fabs(th * a);
-      const double y = fabs(th * b), z = fabs(0.5 * (a + b));
-      if (y < m) m = y;
-      if (z < m) m = z;
-      return copysign(m, a);
-    }
-    return 0.0;
-  }
-  }
-}
 
 struct Bc4 {
   afh_bc bc[4];
@@ -1306,31 +1241,6 @@ __global__ void __launch_bounds__(NT)
   gc2[((size_t)(id - 1) * 4 + (nb - 1)) * nc + (a - 1)] = l2;
 }
 
-struct DevLT {
-  int n_points, n_cols;
-  double x_min, inv_fac;
-  const double *rc;
-};
-
-// LT_get_loc + LT_get_col_at_loc (m_lookup_table.f90:330-406)
-__device__ __forceinline__ double lt_col(const DevLT &lt, int col, double x) {
-  const double frac = (x - lt.x_min) * lt.inv_fac;
-  int low;
-  double lf;
-  if (frac <= 0) {
-    low = 1;
-    lf = 1;
-  } else if (frac >= lt.n_points - 1) {
-    low = lt.n_points - 1;
-    lf = 0;
-  } else {
-    low = (int)ceil(frac);
-    lf = low - frac;
-  }
-  const double *r = lt.rc + (size_t)(col - 1) * lt.n_points;
-  return lf * r[low - 1] + (1 - lf) * r[low];
-}
-
 struct FluxArgs {
   const double *ne, *E, *Ef;
   double *F;
@@ -1577,12 +1487,6 @@ __global__ void k2_consistent_cyl(double *__restrict__ F, const afh_box_meta *__
   consistent_body<true>(F, meta, tasks, ntask, nc, fsz);
 }
 
-struct DevReaction {
-  int rate_type, table_col, n_in, n_out;
-  double rate_factor, c[4];
-  int ix_in[4], ix_out[4], mult_out[4];
-};
-
 struct UpdArgs {
   int ns, nr, n_prev, last_step, e_index;
   double w_prev[MAXPREV];
@@ -1595,23 +1499,19 @@ struct UpdArgs {
   double inv_N, dt, dt_chemistry_nmin;
 };
 
-// get_rates for the field forms (src/m_chemistry.f90:565-620)
+// get_rates (the field forms; afh_fluid_create refuses the others)
 __device__ __forceinline__ double rate_of(const UpdArgs &A, const DevReaction &R,
                                           double field) {
+  const auto tab = [&](int col) { return lt_col(A.chem, col, field); };
   const double c0 = R.rate_factor;
   const double *c = R.c;
   switch (R.rate_type) {
-  case AFH_RATE_TABULATED_FIELD: return c0 * lt_col(A.chem, R.table_col, field);
-  case AFH_RATE_CONSTANT: return c0 * c[0];
-  case AFH_RATE_LINEAR: return c0 * c[0] * (field - c[1]);
-  case AFH_RATE_EXP_V1: {
-    const double z = c[1] / (c[2] + field);
-    return c0 * c[0] * exp(-(z * z));
-  }
-  default: {  // AFH_RATE_EXP_V2
-    const double z = field / c[1];
-    return c0 * c[0] * exp(-(z * z));
-  }
+  case AFH_RATE_TABULATED_FIELD:
+    return field_form<AFH_RATE_TABULATED_FIELD>(c0, c, R.table_col, field, tab);
+  case AFH_RATE_CONSTANT: return field_form<AFH_RATE_CONSTANT>(c0, c, 0, field, tab);
+  case AFH_RATE_LINEAR: return field_form<AFH_RATE_LINEAR>(c0, c, 0, field, tab);
+  case AFH_RATE_EXP_V1: return field_form<AFH_RATE_EXP_V1>(c0, c, 0, field, tab);
+  default: return field_form<AFH_RATE_EXP_V2>(c0, c, 0, field, tab);
   }
 }
 
@@ -1674,17 +1574,6 @@ struct SrcFacArgs {
   DevLT td;
 };
 
-// NORM2 of (a, b) as the Fortran runtime of the reference build evaluates it:
-// the largest magnitude m, the other over m squared; m sqrt(1 + s) -- not
-// sqrt(a a + b b), which differs in the last bit for about a third of all
-// inputs (afh.electrode.norm2 on the host)
-__device__ __forceinline__ double norm2_2(double a, double b) {
-  a = fabs(a), b = fabs(b);
-  if (a == 0.0) return b * sqrt(1 + 0.0);
-  const double t = b > a ? a / b : b / a;
-  return (b > a ? b : a) * sqrt(1 + t * t);
-}
-
 // f(std::true_type or std::false_type) for the run-time flag on
 template <class F> inline void with_flag(bool on, F &&f) {
   if (on) f(std::true_type{});
@@ -1715,35 +1604,11 @@ struct RateSumArgs {
   const double *Ef;  // face field
 };
 
-// the wave's sum in a fixed order (the xor butterfly: every lane ends with
-// the same bits); every lane of the wave must be active
-__device__ __forceinline__ double wave_sum(double v) {
-  for (int o = 32; o > 0; o >>= 1) v = v + __shfl_xor(v, o, 64);
-  return v;
-}
-// the wave partials of a k2_update<..., RATES> workgroup: [nr + 1][4 waves]
-__device__ __forceinline__ double *rate_sum_lds() {
-  __shared__ double w[(AFH_MAX_REACTIONS + 1) * 4];
-  return w;
-}
-
-// adds the rows of part in a fixed order: one workgroup per column (reaction,
-// J.E), lane q the rows q, q + NT, ... in turn, then the lanes' sums by
-// halving through LDS
 __global__ void __launch_bounds__(NT)
     k2_rate_fold(const double *__restrict__ part, int n_rows, int n_col,
                  double *__restrict__ out) {
-  const int c = blockIdx.x;
-  double s = 0.0;
-  for (int r = threadIdx.x; r < n_rows; r += NT) s = s + part[(size_t)r * n_col + c];
-  __shared__ double w[NT];
-  w[threadIdx.x] = s;
-  __syncthreads();
-  for (int h = NT / 2; h > 0; h >>= 1) {
-    if ((int)threadIdx.x < h) w[threadIdx.x] = w[threadIdx.x] + w[threadIdx.x + h];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[c] = w[0];
+  static_assert(NT == 256, "rate_fold's workgroup");
+  rate_fold(part, n_rows, n_col, out);
 }
 
 template <bool PHOTO, bool MASK, bool IONS, bool SRCFAC = false, bool RATES = false>
@@ -2060,13 +1925,6 @@ __global__ void k2_red_fold(unsigned long long *red, int slot0, int n, int is_ma
   }
 }
 
-struct LevelList {
-  std::vector<int32_t> off;
-  int32_t *d = nullptr;
-  int n(int lvl) const { return off[lvl] - off[lvl - 1]; }
-  const int32_t *at(int lvl) const { return d + off[lvl - 1]; }
-};
-
 struct Meth {
   int set = 0;
   afh_bc bc[4];
@@ -2117,6 +1975,7 @@ struct afh_tree {
   std::vector<int> auto_vars;  // tree%cc_auto_vars (afh_set_cc_prolong order)
   std::vector<double> lvl_dr;  // 2 per level
   double *d_boxred = nullptr;  // per-leaf (value, cell) of afh_tree_sum_cc / reduce_loc
+  int boxred_cap = 0;
   uint8_t *d_leaf = nullptr;   // per box id: a leaf (k2_photoi_sum; made on first use)
   // results of the afivo_hip_analysis.h reductions on the device (an_cap
   // doubles): 4 for a value and its place, then the list of local maxima
@@ -2124,11 +1983,7 @@ struct afh_tree {
   size_t an_cap = 0;
   // kernel timing (afh_profile_enable/read, as in libafivo_hip): HIP events
   // around every launch of one kernel class on the tree's stream
-  int prof_class = 0;
-  std::vector<hipEvent_t> ev_pool;
-  size_t ev_used = 0;
-  double prof_bytes = 0;
-  int64_t prof_launches = 0;
+  Prof prof;
   double *ccv(int iv) const { return cc + (size_t)(iv - 1) * nb * bsz; }
   double *fcv(int ivf) const { return fc + (size_t)(ivf - 1) * nb * fsz; }
   Bc4 bc4(int iv) const {
@@ -2225,12 +2080,7 @@ struct afh_fluid {
   int sf_mode = 0, sf_iv = 0;
   double sf_min_e = 0.0;
   uint8_t *d_sf_ion = nullptr;
-  // afh_fluid_set_rate_sums: on, the workgroups' partial rows (rs_cap rows of
-  // n_reactions + 1 doubles), the folded result on the device and whether a
-  // last step has filled it
-  bool rs_on = false, rs_valid = false;
-  double *d_rs_part = nullptr, *d_rs_out = nullptr;
-  size_t rs_cap = 0;
+  RateSums rs;  // afh_fluid_set_rate_sums
 };
 
 namespace afh2 {
@@ -2238,49 +2088,10 @@ namespace afh2 {
 // per-box launches: a workgroup of the work rounded up to whole waves (at
 // most NT lanes), so a small box does not dispatch idle waves (8^2 boxes:
 // one wave per box instead of four)
-static inline int blk2n(int work) { return work >= NT ? NT : ((work + 63) / 64) * 64; }
-static inline dim3 blk2(int work) { return dim3((unsigned)blk2n(work)); }
+static inline dim3 blk2(int work) { return dim3((unsigned)fit_blk(work)); }
 static inline dim3 grid2(int work, int nbox) {
-  const int b = blk2n(work);
+  const int b = fit_blk(work);
   return dim3((unsigned)((work + b - 1) / b), (unsigned)nbox);
-}
-
-static int32_t upload_list(LevelList &L, const std::vector<std::vector<int32_t>> &lists) {
-  L.off.assign(lists.size() + 1, 0);
-  std::vector<int32_t> flat;
-  for (size_t l = 0; l < lists.size(); l++) {
-    flat.insert(flat.end(), lists[l].begin(), lists[l].end());
-    L.off[l + 1] = (int)flat.size();
-  }
-  if (L.d) hipFree(L.d);
-  L.d = nullptr;
-  if (!flat.empty()) {
-    H2(hipMalloc(&L.d, flat.size() * sizeof(int32_t)));
-    H2(hipMemcpy(L.d, flat.data(), flat.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-  }
-  return AFH_OK;
-}
-
-static void prof_mark(afh_tree *t, int kc) {
-  if (t->prof_class != kc) return;
-  if (t->ev_used == t->ev_pool.size()) {
-    hipEvent_t e;
-    hipEventCreate(&e);
-    t->ev_pool.push_back(e);
-  }
-  hipEventRecord(t->ev_pool[t->ev_used++], t->stream);
-}
-
-static void prof_end(afh_tree *t, int kc, double bytes) {
-  if (t->prof_class != kc) return;
-  prof_mark(t, kc);
-  t->prof_bytes += bytes;
-  t->prof_launches++;
-}
-
-static void free_list(LevelList &L) {
-  if (L.d) hipFree(L.d);
-  L.d = nullptr;
 }
 
 // lvl = 0: every level in one launch (afh_gc_tree without refinement
@@ -2294,16 +2105,16 @@ static int32_t gc_lvl(afh_tree *t, int lvl, int iv, bool corners) {
     hipLaunchKernelGGL(k2_gc_box, dim3((n + per - 1) / per), dim3(per > 1 ? per * L : 64), 0,
                        t->stream, t->ccv(iv), t->d_boxes, t->ids.at(lvl), n, per, t->nc,
                        t->bsz, t->bc4(iv));
-    H2_LAUNCH("k2_gc_box");
+    AFH_LAUNCH_CHECK("k2_gc_box");
     return AFH_OK;
   }
   hipLaunchKernelGGL(k2_gc, grid2(4 * t->nc, n), blk2(4 * t->nc), 0, t->stream, t->ccv(iv),
                      t->d_boxes, t->ids.at(lvl), t->nc, t->bsz, t->bc4(iv));
-  H2_LAUNCH("k2_gc");
+  AFH_LAUNCH_CHECK("k2_gc");
   if (corners) {
     hipLaunchKernelGGL(k2_corners, dim3((4 * n + NT - 1) / NT), dim3(NT), 0, t->stream,
                        t->ccv(iv), t->d_boxes, t->ids.at(lvl), n, t->nc, t->bsz);
-    H2_LAUNCH("k2_corners");
+    AFH_LAUNCH_CHECK("k2_corners");
   }
   return AFH_OK;
 }
@@ -2311,8 +2122,8 @@ static int32_t gc_lvl(afh_tree *t, int lvl, int iv, bool corners) {
 // nslot consecutive slots from slot to v, one launch
 static int32_t red_init(afh_tree *t, int slot, double v, int nslot = 1) {
   hipLaunchKernelGGL(k2_red_fill, dim3(nslot), dim3(RED_SHARDS), 0, t->stream,
-                     t->red + (size_t)slot * RED_SHARDS, host_ord(v));
-  H2_LAUNCH("k2_red_fill");
+                     t->red + (size_t)slot * RED_SHARDS, host_dbl_to_ord(v));
+  AFH_LAUNCH_CHECK("k2_red_fill");
   return AFH_OK;
 }
 
@@ -2321,10 +2132,10 @@ static int32_t red_init(afh_tree *t, int slot, double v, int nslot = 1) {
 static int32_t red_read(afh_tree *t, int slot0, int n, int is_max, double *out) {
   hipLaunchKernelGGL(k2_red_fold, dim3(1), dim3(RED_SHARDS), 0, t->stream, t->red, slot0, n,
                      is_max, t->red_out);
-  H2_LAUNCH("k2_red_fold");
-  H2(hipMemcpyAsync(t->h_red, t->red_out, n * sizeof(unsigned long long),
+  AFH_LAUNCH_CHECK("k2_red_fold");
+  AFH_HIP(hipMemcpyAsync(t->h_red, t->red_out, n * sizeof(unsigned long long),
                     hipMemcpyDeviceToHost, t->stream));
-  H2(hipStreamSynchronize(t->stream));
+  AFH_HIP(hipStreamSynchronize(t->stream));
   for (int q = 0; q < n; q++) out[q] = ord_to_dbl(t->h_red[q]);
   return AFH_OK;
 }
@@ -2378,7 +2189,7 @@ int32_t afh_tree_get_coord(afh_tree *t, int32_t *coord) {
   return AFH_OK;
 }
 
-const char *afh_last_error(void) { return afh2::g_err.c_str(); }
+const char *afh_last_error(void) { return afhc::err_text(); }
 
 int32_t afh_tree_create(const afh_tree_desc *desc, int32_t device, afh_tree **out) {
   if (!desc || !out || !desc->boxes) return set_error(AFH_ERR_ARG, "afh_tree_create: null");
@@ -2403,9 +2214,9 @@ int32_t afh_tree_create(const afh_tree_desc *desc, int32_t device, afh_tree **ou
                               desc->coarse_grid_size[q] % nc != 0))
       return set_error(AFH_ERR_ARG, "afh_tree_create: periodic dimension %d of %d cells, "
                        "boxes of %d", q + 1, desc->coarse_grid_size[q], nc);
-  if (device >= 0) H2(hipSetDevice(device));
+  if (device >= 0) AFH_HIP(hipSetDevice(device));
   afh_tree *t = new afh_tree();
-  H2(hipGetDevice(&t->device));
+  AFH_HIP(hipGetDevice(&t->device));
   if (const char *env = getenv("AFH2_GC_BOX")) t->gc_box = atoi(env) != 0;
   if (const char *env = getenv("AFH2_GC_TREE_ONE")) t->gc_tree_one = atoi(env) != 0;
   t->nc = nc, t->ng = nc + 2, t->nb = desc->n_boxes, t->nlvl = desc->highest_lvl;
@@ -2465,20 +2276,20 @@ int32_t afh_tree_create(const afh_tree_desc *desc, int32_t device, afh_tree **ou
       (e = upload_list(t->parents, t->h_parents)) || (e = upload_list(t->refb, refb)) ||
       (e = upload_list(t->children_of, kids)) || (e = upload_list(t->cflux, cfl)))
     return e;
-  H2(hipMalloc(&t->d_boxes, sizeof(afh_box_meta) * t->nb));
-  H2(hipMemcpy(t->d_boxes, t->boxes.data(), sizeof(afh_box_meta) * t->nb,
+  AFH_HIP(hipMalloc(&t->d_boxes, sizeof(afh_box_meta) * t->nb));
+  AFH_HIP(hipMemcpy(t->d_boxes, t->boxes.data(), sizeof(afh_box_meta) * t->nb,
                hipMemcpyHostToDevice));
-  H2(hipMalloc(&t->cc, sizeof(double) * (size_t)t->nvc * t->nb * t->bsz));
-  H2(hipMemset(t->cc, 0, sizeof(double) * (size_t)t->nvc * t->nb * t->bsz));
+  AFH_HIP(hipMalloc(&t->cc, sizeof(double) * (size_t)t->nvc * t->nb * t->bsz));
+  AFH_HIP(hipMemset(t->cc, 0, sizeof(double) * (size_t)t->nvc * t->nb * t->bsz));
   if (t->nvf) {
-    H2(hipMalloc(&t->fc, sizeof(double) * (size_t)t->nvf * t->nb * t->fsz));
-    H2(hipMemset(t->fc, 0, sizeof(double) * (size_t)t->nvf * t->nb * t->fsz));
+    AFH_HIP(hipMalloc(&t->fc, sizeof(double) * (size_t)t->nvf * t->nb * t->fsz));
+    AFH_HIP(hipMemset(t->fc, 0, sizeof(double) * (size_t)t->nvf * t->nb * t->fsz));
   }
-  H2(hipMalloc(&t->gc2, sizeof(double) * (size_t)t->nb * 4 * nc));
-  H2(hipMalloc(&t->red, sizeof(unsigned long long) * RED_SLOTS * RED_SHARDS));
-  H2(hipMalloc(&t->red_out, sizeof(unsigned long long) * RED_SLOTS));
-  H2(hipHostMalloc(&t->h_red, sizeof(unsigned long long) * RED_SLOTS));
-  H2(hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking));
+  AFH_HIP(hipMalloc(&t->gc2, sizeof(double) * (size_t)t->nb * 4 * nc));
+  AFH_HIP(hipMalloc(&t->red, sizeof(unsigned long long) * RED_SLOTS * RED_SHARDS));
+  AFH_HIP(hipMalloc(&t->red_out, sizeof(unsigned long long) * RED_SLOTS));
+  AFH_HIP(hipHostMalloc(&t->h_red, sizeof(unsigned long long) * RED_SLOTS));
+  AFH_HIP(hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking));
   *out = t;
   return AFH_OK;
 }
@@ -2492,7 +2303,7 @@ int32_t afh_tree_destroy(afh_tree *t) {
   hipFree(t->red), hipFree(t->red_out), hipHostFree(t->h_red), hipFree(t->d_boxred);
   hipFree(t->d_an);
   hipFree(t->d_leaf);
-  for (hipEvent_t e : t->ev_pool) hipEventDestroy(e);
+  for (hipEvent_t e : t->prof.ev_pool) hipEventDestroy(e);
   hipStreamDestroy(t->stream);
   delete t;
   return AFH_OK;
@@ -2500,7 +2311,7 @@ int32_t afh_tree_destroy(afh_tree *t) {
 
 int32_t afh_tree_sync(afh_tree *t) {
   if (!t) return set_error(AFH_ERR_ARG, "afh_tree_sync: null");
-  H2(hipStreamSynchronize(t->stream));
+  AFH_HIP(hipStreamSynchronize(t->stream));
   return AFH_OK;
 }
 
@@ -2510,31 +2321,13 @@ int32_t afh_profile_enable(afh_tree *t, int32_t kclass) {
       kclass != AFH_PROF_CS)
     return set_error(AFH_ERR_UNSUPPORTED, "afh_profile_enable: class %d (2-D: GSRB, FLUX, CS)",
                      kclass);
-  H2(hipStreamSynchronize(t->stream));
-  t->prof_class = kclass;
-  t->ev_used = 0;
-  t->prof_bytes = 0;
-  t->prof_launches = 0;
-  return AFH_OK;
+  return profile_enable(t, kclass);
 }
 
 int32_t afh_profile_read(afh_tree *t, double *total_ms, int64_t *launches, double *bytes) {
   if (!t || !total_ms || !launches || !bytes)
     return set_error(AFH_ERR_ARG, "afh_profile_read: null argument");
-  H2(hipStreamSynchronize(t->stream));
-  double ms = 0;
-  for (size_t q = 0; q + 1 < t->ev_used; q += 2) {
-    float e = 0;
-    H2(hipEventElapsedTime(&e, t->ev_pool[q], t->ev_pool[q + 1]));
-    ms += e;
-  }
-  *total_ms = ms;
-  *launches = t->prof_launches;
-  *bytes = t->prof_bytes;
-  t->ev_used = 0;
-  t->prof_bytes = 0;
-  t->prof_launches = 0;
-  return AFH_OK;
+  return profile_read(t, total_ms, launches, bytes);
 }
 
 int32_t afh_set_cc_methods(afh_tree *t, int32_t iv, const afh_bc *bc, int32_t rb,
@@ -2572,33 +2365,33 @@ int32_t afh_set_bc(afh_tree *t, int32_t iv, int32_t nb, int32_t type, double val
 
 int32_t afh_cc_put(afh_tree *t, int32_t iv, const double *host) {
   if (int32_t e = check_iv(t, iv, "afh_cc_put")) return e;
-  H2(hipMemcpyAsync(t->ccv(iv), host, sizeof(double) * (size_t)t->nb * t->bsz,
+  AFH_HIP(hipMemcpyAsync(t->ccv(iv), host, sizeof(double) * (size_t)t->nb * t->bsz,
                     hipMemcpyHostToDevice, t->stream));
-  H2(hipStreamSynchronize(t->stream));
+  AFH_HIP(hipStreamSynchronize(t->stream));
   return AFH_OK;
 }
 
 int32_t afh_cc_get(afh_tree *t, int32_t iv, double *host) {
   if (int32_t e = check_iv(t, iv, "afh_cc_get")) return e;
-  H2(hipMemcpyAsync(host, t->ccv(iv), sizeof(double) * (size_t)t->nb * t->bsz,
+  AFH_HIP(hipMemcpyAsync(host, t->ccv(iv), sizeof(double) * (size_t)t->nb * t->bsz,
                     hipMemcpyDeviceToHost, t->stream));
-  H2(hipStreamSynchronize(t->stream));
+  AFH_HIP(hipStreamSynchronize(t->stream));
   return AFH_OK;
 }
 
 int32_t afh_fc_put(afh_tree *t, int32_t ivf, const double *host) {
   if (!t || ivf < 1 || ivf > t->nvf) return set_error(AFH_ERR_ARG, "afh_fc_put: bad variable");
-  H2(hipMemcpyAsync(t->fcv(ivf), host, sizeof(double) * (size_t)t->nb * t->fsz,
+  AFH_HIP(hipMemcpyAsync(t->fcv(ivf), host, sizeof(double) * (size_t)t->nb * t->fsz,
                     hipMemcpyHostToDevice, t->stream));
-  H2(hipStreamSynchronize(t->stream));
+  AFH_HIP(hipStreamSynchronize(t->stream));
   return AFH_OK;
 }
 
 int32_t afh_fc_get(afh_tree *t, int32_t ivf, double *host) {
   if (!t || ivf < 1 || ivf > t->nvf) return set_error(AFH_ERR_ARG, "afh_fc_get: bad variable");
-  H2(hipMemcpyAsync(host, t->fcv(ivf), sizeof(double) * (size_t)t->nb * t->fsz,
+  AFH_HIP(hipMemcpyAsync(host, t->fcv(ivf), sizeof(double) * (size_t)t->nb * t->fsz,
                     hipMemcpyDeviceToHost, t->stream));
-  H2(hipStreamSynchronize(t->stream));
+  AFH_HIP(hipStreamSynchronize(t->stream));
   return AFH_OK;
 }
 
@@ -2625,7 +2418,7 @@ int32_t afh_restrict_tree(afh_tree *t, int32_t iv) {
     const int n = t->children_of.n(l);
     if (!n) continue;
     restrict_boxes(t, t->ccv(iv), t->children_of.at(l), n, true);
-    H2_LAUNCH("k2_restrict");
+    AFH_LAUNCH_CHECK("k2_restrict");
   }
   return AFH_OK;
 }
@@ -2633,7 +2426,7 @@ int32_t afh_restrict_tree(afh_tree *t, int32_t iv) {
 int32_t afh_tree_copy_cc(afh_tree *t, int32_t iv_from, int32_t iv_to) {
   if (int32_t e = check_iv(t, iv_from, "afh_tree_copy_cc")) return e;
   if (int32_t e = check_iv(t, iv_to, "afh_tree_copy_cc")) return e;
-  H2(hipMemcpyAsync(t->ccv(iv_to), t->ccv(iv_from), sizeof(double) * (size_t)t->nb * t->bsz,
+  AFH_HIP(hipMemcpyAsync(t->ccv(iv_to), t->ccv(iv_from), sizeof(double) * (size_t)t->nb * t->bsz,
                     hipMemcpyDeviceToDevice, t->stream));
   return AFH_OK;
 }
@@ -2647,7 +2440,7 @@ int32_t afh_tree_maxabs_cc(afh_tree *t, int32_t iv, double *out) {
     if (!n) continue;
     hipLaunchKernelGGL(k2_maxabs, grid2(t->nc * t->nc, n), blk2(t->nc * t->nc), 0, t->stream, t->ccv(iv),
                        t->leaves.at(l), t->nc, t->bsz, t->red + 3 * RED_SHARDS);
-    H2_LAUNCH("k2_maxabs");
+    AFH_LAUNCH_CHECK("k2_maxabs");
   }
   return red_read(t, 3, 1, 1, out);
 }
@@ -2701,19 +2494,19 @@ int32_t afh_mg_create(afh_tree *t, const afh_mg_desc *d, afh_mg **out) {
     c.c[0] = -s - d->helmholtz_lambda;
     c.inv_c1 = 1 / c.c[0];
   }
-  H2(hipMalloc(&mg->d_lvl_c, sizeof(Coef2) * t->nlvl));
-  H2(hipMemcpy(mg->d_lvl_c, mg->lvl_c.data(), sizeof(Coef2) * t->nlvl, hipMemcpyHostToDevice));
+  AFH_HIP(hipMalloc(&mg->d_lvl_c, sizeof(Coef2) * t->nlvl));
+  AFH_HIP(hipMemcpy(mg->d_lvl_c, mg->lvl_c.data(), sizeof(Coef2) * t->nlvl, hipMemcpyHostToDevice));
   if (const char *env = getenv("AFH2_ALL_LVL")) mg->all_lvl = atoi(env) != 0;
   if (const char *env = getenv("AFH2_GRAPHS")) mg->use_graphs = atoi(env) != 0;
   if (const char *env = getenv("AFH2_CORNER_FOLD")) mg->corner_fold = atoi(env) != 0;
-  H2(hipMalloc(&mg->d_q[0], sizeof(double) * nx * nx));
-  H2(hipMalloc(&mg->d_q[1], sizeof(double) * ny * ny));
-  H2(hipMalloc(&mg->d_e[0], sizeof(double) * nx));
-  H2(hipMalloc(&mg->d_e[1], sizeof(double) * ny));
+  AFH_HIP(hipMalloc(&mg->d_q[0], sizeof(double) * nx * nx));
+  AFH_HIP(hipMalloc(&mg->d_q[1], sizeof(double) * ny * ny));
+  AFH_HIP(hipMalloc(&mg->d_e[0], sizeof(double) * nx));
+  AFH_HIP(hipMalloc(&mg->d_e[1], sizeof(double) * ny));
   if (const char *env = getenv("AFH_PAIR2D")) mg->pair = atoi(env) != 0;
   mg->pair = mg->pair && (t->nc == 4 || t->nc == 8 || t->nc == 16) &&
              d->n_cycle_down % 2 == 0 && d->n_cycle_up % 2 == 0;
-  if (mg->pair) H2(hipMalloc(&mg->alt, sizeof(double) * (size_t)t->nb * t->bsz));
+  if (mg->pair) AFH_HIP(hipMalloc(&mg->alt, sizeof(double) * (size_t)t->nb * t->bsz));
   mg->h_vp.assign(t->nb, nullptr), mg->h_bp.assign(t->nb, nullptr);
   mg->h_dd.assign(t->nb, nullptr), mg->h_bv.assign(t->nb, nullptr);
   mg->h_ix.assign(t->nb, nullptr), mg->h_lsf_n.assign(t->nb, 0);
@@ -2756,18 +2549,18 @@ static int32_t prepare_var(afh_mg *mg) {
   if (!mg->var_dirty) return AFH_OK;
   afh_tree *t = mg->t;
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  H2(hipStreamIsCapturing(t->stream, &cs));
+  AFH_HIP(hipStreamIsCapturing(t->stream, &cs));
   if (cs != hipStreamCaptureStatusNone)
     return set_error(AFH_ERR_STATE, "electrode stencils changed during a graph capture");
   mg->var_dirty = false;
-  H2(hipStreamSynchronize(t->stream));
+  AFH_HIP(hipStreamSynchronize(t->stream));
   for (auto &g : mg->graphs)
     if (g.second.exec) hipGraphExecDestroy(g.second.exec);
   mg->graphs.clear();
   const int nb = t->nb, nl = t->nlvl;
   auto table = [&](auto **d, const auto &h) -> int32_t {
-    if (!*d) H2(hipMalloc(d, sizeof(h[0]) * nb));
-    H2(hipMemcpy(*d, h.data(), sizeof(h[0]) * nb, hipMemcpyHostToDevice));
+    if (!*d) AFH_HIP(hipMalloc(d, sizeof(h[0]) * nb));
+    AFH_HIP(hipMemcpy(*d, h.data(), sizeof(h[0]) * nb, hipMemcpyHostToDevice));
     return AFH_OK;
   };
   int32_t e;
@@ -2836,7 +2629,7 @@ static int32_t solve_coarse_pfmg(afh_mg *mg) {
   fresh = fresh || mg->pf_v1_gen != mg->v1_gen;  // a level-1 stencil changed
   if (fresh) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    H2(hipStreamIsCapturing(t->stream, &cs));
+    AFH_HIP(hipStreamIsCapturing(t->stream, &cs));
     if (cs != hipStreamCaptureStatusNone)
       return set_error(AFH_ERR_STATE, "pfmg: setup changed during a graph capture");
     std::vector<double> a7(7 * n0, 0.0), b2r(4 * n0, 0.0);
@@ -2893,22 +2686,22 @@ static int32_t solve_coarse_pfmg(afh_mg *mg) {
     afh_pf::pf_device_tables(h, lv, A, P);
     const size_t np = h.off[h.nl];
     afh_pfmg_free(&h);
-    H2(hipStreamSynchronize(t->stream));
+    AFH_HIP(hipStreamSynchronize(t->stream));
     hipFree(mg->d_pf_lvl), hipFree(mg->d_pf_A), hipFree(mg->d_pf_P);
-    H2(hipMalloc(&mg->d_pf_lvl, sizeof(afh_pf::PfLvl) * lv.size()));
-    H2(hipMalloc(&mg->d_pf_A, sizeof(double) * A.size()));
-    H2(hipMalloc(&mg->d_pf_P, sizeof(double) * P.size()));
+    AFH_HIP(hipMalloc(&mg->d_pf_lvl, sizeof(afh_pf::PfLvl) * lv.size()));
+    AFH_HIP(hipMalloc(&mg->d_pf_A, sizeof(double) * A.size()));
+    AFH_HIP(hipMalloc(&mg->d_pf_P, sizeof(double) * P.size()));
     if (!mg->d_pf_b2r) {
-      H2(hipMalloc(&mg->d_pf_b2r, sizeof(double) * 4 * n0));
-      H2(hipMalloc(&mg->d_pf_fmask, n0));
-      H2(hipMalloc(&mg->d_pf_iters, sizeof(int)));
+      AFH_HIP(hipMalloc(&mg->d_pf_b2r, sizeof(double) * 4 * n0));
+      AFH_HIP(hipMalloc(&mg->d_pf_fmask, n0));
+      AFH_HIP(hipMalloc(&mg->d_pf_iters, sizeof(int)));
     }
-    H2(hipMemcpy(mg->d_pf_lvl, lv.data(), sizeof(afh_pf::PfLvl) * lv.size(),
+    AFH_HIP(hipMemcpy(mg->d_pf_lvl, lv.data(), sizeof(afh_pf::PfLvl) * lv.size(),
                  hipMemcpyHostToDevice));
-    H2(hipMemcpy(mg->d_pf_A, A.data(), sizeof(double) * A.size(), hipMemcpyHostToDevice));
-    H2(hipMemcpy(mg->d_pf_P, P.data(), sizeof(double) * P.size(), hipMemcpyHostToDevice));
-    H2(hipMemcpy(mg->d_pf_b2r, b2r.data(), sizeof(double) * b2r.size(), hipMemcpyHostToDevice));
-    H2(hipMemcpy(mg->d_pf_fmask, fm.data(), n0, hipMemcpyHostToDevice));
+    AFH_HIP(hipMemcpy(mg->d_pf_A, A.data(), sizeof(double) * A.size(), hipMemcpyHostToDevice));
+    AFH_HIP(hipMemcpy(mg->d_pf_P, P.data(), sizeof(double) * P.size(), hipMemcpyHostToDevice));
+    AFH_HIP(hipMemcpy(mg->d_pf_b2r, b2r.data(), sizeof(double) * b2r.size(), hipMemcpyHostToDevice));
+    AFH_HIP(hipMemcpy(mg->d_pf_fmask, fm.data(), n0, hipMemcpyHostToDevice));
     (void)np;
     mg->pf_nl = (int)lv.size();
     mg->pf_wave = afh_pf::pf_wave_from(lv);
@@ -2921,10 +2714,10 @@ static int32_t solve_coarse_pfmg(afh_mg *mg) {
       static std::mutex m;
       static std::map<int, int> top;
       int dev = 0;
-      H2(hipGetDevice(&dev));
+      AFH_HIP(hipGetDevice(&dev));
       std::lock_guard<std::mutex> g(m);
       if (mg->pf_lds > top[dev]) {
-        H2(hipFuncSetAttribute((const void *)k2_cs_pfmg,
+        AFH_HIP(hipFuncSetAttribute((const void *)k2_cs_pfmg,
                                hipFuncAttributeMaxDynamicSharedMemorySize, mg->pf_lds));
         top[dev] = mg->pf_lds;
       }
@@ -2933,14 +2726,14 @@ static int32_t solve_coarse_pfmg(afh_mg *mg) {
     mg->pf_v1_gen = mg->v1_gen;
   }
   const int nt = std::min(1024, std::max(256, (int)((n0 + 63) / 64 * 64)));
-  prof_mark(t, AFH_PROF_CS);
+  prof_begin(t, AFH_PROF_CS);
   hipLaunchKernelGGL(k2_cs_pfmg, dim3(1), dim3(nt), mg->pf_lds, t->stream, mg->d_pf_lvl,
                      mg->pf_nl, mg->pf_wave, mg->d_pf_A, mg->d_pf_P, mg->d_pf_b2r, mg->d_pf_fmask,
                      t->ccv(mg->d.i_phi), t->ccv(mg->d.i_rhs), t->d_boxes, t->ids.at(1), nid,
                      t->nc, t->bsz, t->bc4(mg->d.i_phi), mg->d.coarse_tol, mg->d.coarse_cycles,
                      mg->d_pf_iters,
                      mg->any_var && mg->lvl_var[0] ? (const double *const *)mg->d_bp : nullptr);
-  H2_LAUNCH("k2_cs_pfmg");
+  AFH_LAUNCH_CHECK("k2_cs_pfmg");
   prof_end(t, AFH_PROF_CS, 0.0);
   return gc_lvl(t, 1, mg->d.i_phi, true);
 }
@@ -2959,15 +2752,15 @@ static int32_t solve_coarse(afh_mg *mg) {
     fresh = fresh || (!t->periodic[q >> 1] && mg->q_bc[q] != M.bc[q].type);
   const double hx = mg->lvl_c[0].c[1], hy = mg->lvl_c[0].c[3];
   if (fresh) {
-    H2(hipStreamSynchronize(t->stream));
+    AFH_HIP(hipStreamSynchronize(t->stream));
     const int n[2] = {mg->nx, mg->ny};
     const double h[2] = {hx, hy};
     for (int d = 0; d < 2; d++) {
       std::vector<double> q((size_t)n[d] * n[d]), e(n[d]);
       afh2_cs_tables(n[d], M.bc[2 * d].type, M.bc[2 * d + 1].type, t->periodic[d], h[d],
                      q.data(), e.data());
-      H2(hipMemcpy(mg->d_q[d], q.data(), sizeof(double) * q.size(), hipMemcpyHostToDevice));
-      H2(hipMemcpy(mg->d_e[d], e.data(), sizeof(double) * e.size(), hipMemcpyHostToDevice));
+      AFH_HIP(hipMemcpy(mg->d_q[d], q.data(), sizeof(double) * q.size(), hipMemcpyHostToDevice));
+      AFH_HIP(hipMemcpy(mg->d_e[d], e.data(), sizeof(double) * e.size(), hipMemcpyHostToDevice));
     }
     for (int q = 0; q < 4; q++) mg->q_bc[q] = M.bc[q].type;
     mg->q_built = true;
@@ -2977,7 +2770,7 @@ static int32_t solve_coarse(afh_mg *mg) {
                      mg->nx, mg->ny, hx, hy, t->bc4(mg->d.i_phi), mg->d_q[0], mg->d_q[1],
                      mg->d_e[0], mg->d_e[1], mg->d.helmholtz_lambda,
                      t->periodic[0] | (t->periodic[1] << 1));
-  H2_LAUNCH("k2_cs_direct");
+  AFH_LAUNCH_CHECK("k2_cs_direct");
   return gc_lvl(t, 1, mg->d.i_phi, true);
 }
 
@@ -3029,9 +2822,9 @@ static int32_t gsrb_boxes(afh_mg *mg, int lvl, bool up, bool skip_corners = fals
       // timed on levels of >= 256 boxes without electrode boxes, as the split
       // half-sweeps
       const int pc = n >= 256 && !var ? AFH_PROF_GSRB : -1;
-      prof_mark(t, pc);
+      prof_begin(t, pc);
       pair_launch(mg, lvl, var, (p & 1) ? mg->alt : phi, (p & 1) ? phi : mg->alt, 2 * p);
-      H2_LAUNCH("k2_pair_box");
+      AFH_LAUNCH_CHECK("k2_pair_box");
       // a red+black pair reads phi and rhs and writes phi once = 24 B/cell
       prof_end(t, pc, 24.0 * t->nc * t->nc * n);
     }
@@ -3040,12 +2833,12 @@ static int32_t gsrb_boxes(afh_mg *mg, int lvl, bool up, bool skip_corners = fals
       hipLaunchKernelGGL(k2_rhs_roundtrip, grid2(t->nc * t->nc, nv), blk2(t->nc * t->nc), 0,
                          t->stream, t->ccv(mg->d.i_rhs), mg->ids_v.at(lvl), t->nc, t->bsz,
                          mg->d_bp, 2 * nc_);
-      H2_LAUNCH("k2_rhs_roundtrip");
+      AFH_LAUNCH_CHECK("k2_rhs_roundtrip");
     }
     if (up && !skip_corners) {
       hipLaunchKernelGGL(k2_corners, dim3((4 * n + NT - 1) / NT), dim3(NT), 0, t->stream,
                          phi, t->d_boxes, t->ids.at(lvl), n, t->nc, t->bsz);
-      H2_LAUNCH("k2_corners");
+      AFH_LAUNCH_CHECK("k2_corners");
     }
     return AFH_OK;
   }
@@ -3059,7 +2852,7 @@ static int32_t gsrb_boxes(afh_mg *mg, int lvl, bool up, bool skip_corners = fals
       // libafivo_hip's pair: the small levels' launches are launch-bound,
       // another regime
       const int pc = n >= 256 && !var ? AFH_PROF_GSRB : -1;
-      prof_mark(t, pc);
+      prof_begin(t, pc);
       if (t->cyl())
         hipLaunchKernelGGL(k2_gsrb<StCyl>, grid2(w, ncst), blk2(w), cyl_lds(t), t->stream,
                            t->ccv(mg->d.i_phi), t->ccv(mg->d.i_rhs), L.at(lvl), t->nc, t->bsz,
@@ -3068,14 +2861,14 @@ static int32_t gsrb_boxes(afh_mg *mg, int lvl, bool up, bool skip_corners = fals
         hipLaunchKernelGGL(k2_gsrb<StConst>, grid2(w, ncst), blk2(w), 0, t->stream,
                            t->ccv(mg->d.i_phi), t->ccv(mg->d.i_rhs), L.at(lvl), t->nc, t->bsz,
                            StConst{mg->lvl_c[lvl - 1]}, s, StConst::Meta{});
-      H2_LAUNCH("k2_gsrb");
+      AFH_LAUNCH_CHECK("k2_gsrb");
       prof_end(t, pc, 16.0 * t->nc * t->nc * n);
     }
     if (var) {
       hipLaunchKernelGGL(k2_gsrb_v, grid2(2 * w, nv), blk2(2 * w), 0, t->stream,
                          t->ccv(mg->d.i_phi), t->ccv(mg->d.i_rhs), mg->ids_v.at(lvl), t->nc,
                          t->bsz, mg->d_vp, mg->d_bp, s);
-      H2_LAUNCH("k2_gsrb_v");
+      AFH_LAUNCH_CHECK("k2_gsrb_v");
     }
     if (int32_t e = gc_lvl(t, lvl, mg->d.i_phi, up && s == 2 * nc_)) return e;
   }
@@ -3099,7 +2892,7 @@ static int32_t parent_rhs(afh_mg *mg, int lvl, int copy) {
   };
   launch(L, false);
   if (mg->any_var) launch(mg->parents_v, true);
-  H2_LAUNCH("k2_parent_rhs");
+  AFH_LAUNCH_CHECK("k2_parent_rhs");
   return AFH_OK;
 }
 
@@ -3118,7 +2911,7 @@ static int32_t update_coarse(afh_mg *mg, int lvl) {
   };
   launch(L, false);
   if (mg->any_var) launch(mg->ids_v, true);
-  H2_LAUNCH("k2_rstr_fas");
+  AFH_LAUNCH_CHECK("k2_rstr_fas");
   if (int32_t e = gc_lvl(t, lvl - 1, mg->d.i_phi, true)) return e;
   return parent_rhs(mg, lvl - 1, 1);
 }
@@ -3132,16 +2925,16 @@ static int32_t correct_children(afh_mg *mg, int lvl, bool corners = false) {
   if (corners) {
     hipLaunchKernelGGL(k2_block_corners, grid2(t->bsz, np), blk2(t->bsz), 0, t->stream, tmp,
                        phi, t->d_boxes, t->parents.at(lvl - 1), t->nc, t->bsz);
-    H2_LAUNCH("k2_block_corners");
+    AFH_LAUNCH_CHECK("k2_block_corners");
   } else {
     hipLaunchKernelGGL(k2_block, grid2(t->bsz, np), blk2(t->bsz), 0, t->stream, tmp, phi, tmp,
                        t->parents.at(lvl - 1), t->bsz, 0);
-    H2_LAUNCH("k2_block");
+    AFH_LAUNCH_CHECK("k2_block");
   }
   const int nk = t->children_of.n(lvl - 1);
   hipLaunchKernelGGL(k2_prolong, grid2(t->nc * t->nc, nk), blk2(t->nc * t->nc), 0, t->stream, phi, tmp,
                      t->d_boxes, t->children_of.at(lvl - 1), t->nc, t->bsz);
-  H2_LAUNCH("k2_prolong");
+  AFH_LAUNCH_CHECK("k2_prolong");
   return AFH_OK;
 }
 
@@ -3170,7 +2963,7 @@ static int32_t residual_launch(afh_mg *mg, const LevelList &B, bool var, int l0,
                        t->nc, t->bsz, st, fold ? t->red + 3 * RED_SHARDS : nullptr,
                        all ? mg->d_lvl_c : nullptr, t->d_boxes);
   });
-  H2_LAUNCH("k2_residual");
+  AFH_LAUNCH_CHECK("k2_residual");
   return AFH_OK;
 }
 
@@ -3242,7 +3035,7 @@ static int32_t vcycle_run(afh_mg *mg, bool set_residual, int max_lvl, bool max_o
   // a changed electrode stencil drops the captured graphs: this call runs
   // eagerly and the next one captures again
   if (int32_t e = prepare_var(mg)) return e;
-  if (!mg->use_graphs || t->prof_class) return vcycle(mg, set_residual, max_lvl, max_out);
+  if (!mg->use_graphs || t->prof.cls) return vcycle(mg, set_residual, max_lvl, max_out);
   const int key = (max_lvl << 2) | (set_residual ? 2 : 0) | (max_out ? 1 : 0);
   afh_mg::Graph &g = mg->graphs[key];
   if (g.gen != t->meth_gen) {
@@ -3256,19 +3049,19 @@ static int32_t vcycle_run(afh_mg *mg, bool set_residual, int max_lvl, bool max_o
   }
   if (!g.exec) {
     hipGraph_t graph;
-    H2(hipStreamBeginCapture(t->stream, hipStreamCaptureModeThreadLocal));
+    AFH_HIP(hipStreamBeginCapture(t->stream, hipStreamCaptureModeThreadLocal));
     const int32_t e = vcycle(mg, set_residual, max_lvl, max_out);
     const hipError_t ce = hipStreamEndCapture(t->stream, &graph);
     if (e) {
       if (ce == hipSuccess) hipGraphDestroy(graph);
       return e;
     }
-    H2(ce);
+    AFH_HIP(ce);
     const hipError_t ie = hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0);
     hipGraphDestroy(graph);
-    H2(ie);
+    AFH_HIP(ie);
   }
-  H2(hipGraphLaunch(g.exec, t->stream));
+  AFH_HIP(hipGraphLaunch(g.exec, t->stream));
   return AFH_OK;
 }
 
@@ -3312,7 +3105,7 @@ int32_t afh_mg_fas_fmg(afh_mg *mg, int32_t set_residual, int32_t have_guess) {
         // mg_box_rstr_lpl: tmp with geometry, phi without
         restrict_boxes(t, tmp, t->ids.at(l), n, true);
         restrict_boxes(t, phi, t->ids.at(l), n, false);
-        H2_LAUNCH("k2_restrict");
+        AFH_LAUNCH_CHECK("k2_restrict");
       }
       if ((e = gc_lvl(t, l - 1, mg->d.i_phi, true))) return e;
       if ((e = parent_rhs(mg, l - 1, 0))) return e;
@@ -3326,20 +3119,20 @@ int32_t afh_mg_fas_fmg(afh_mg *mg, int32_t set_residual, int32_t have_guess) {
                          (const double *)nullptr, (const double *)nullptr, t->ids.at(l),
                          t->bsz, 2);
       restrict_boxes(t, rhs, t->ids.at(l), n, true);
-      H2_LAUNCH("k2_restrict");
+      AFH_LAUNCH_CHECK("k2_restrict");
     }
   }
   const int n1 = t->ids.n(1);
   hipLaunchKernelGGL(k2_block, grid2(t->bsz, n1), blk2(t->bsz), 0, t->stream, tmp, phi,
                      (const double *)nullptr, t->ids.at(1), t->bsz, 1);
-  H2_LAUNCH("k2_block");
+  AFH_LAUNCH_CHECK("k2_block");
   if ((e = vcycle(mg, set_residual && t->nlvl == 1, 1, false))) return e;
   for (int l = 2; l <= t->nlvl; l++) {
     const int n = t->ids.n(l);
     if (n) {
       hipLaunchKernelGGL(k2_block, grid2(t->bsz, n), blk2(t->bsz), 0, t->stream, tmp, phi,
                          (const double *)nullptr, t->ids.at(l), t->bsz, 1);
-      H2_LAUNCH("k2_block");
+      AFH_LAUNCH_CHECK("k2_block");
     }
     if ((e = correct_children(mg, l)) || (e = gc_lvl(t, l, mg->d.i_phi, true)) ||
         (e = vcycle(mg, set_residual && l == t->nlvl, l, false)))
@@ -3360,11 +3153,11 @@ int32_t afh_mg_compute_phi_gradient(afh_mg *mg, int32_t i_fc, double fac, int32_
   auto lsf_part = [&]() -> int32_t {
     const int n = mg->any_lsf ? mg->lsf_leaves.off[t->nlvl] - mg->lsf_leaves.off[0] : 0;
     if (!n) return AFH_OK;
-    hipLaunchKernelGGL(k2_lsf_gradient, dim3(n), dim3(blk2n(t->nc * t->nc)), 0, t->stream,
+    hipLaunchKernelGGL(k2_lsf_gradient, dim3(n), dim3(fit_blk(t->nc * t->nc)), 0, t->stream,
                        t->ccv(mg->d.i_phi), t->ccv(mg->i_lsf), t->fcv(i_fc),
                        i_norm ? t->ccv(i_norm) : nullptr, mg->lsf_leaves.at(1), t->d_boxes,
                        t->nc, t->bsz, t->fsz, mg->d_lsf_n, mg->d_ix, mg->d_dd, mg->d_bv, fac);
-    H2_LAUNCH("k2_lsf_gradient");
+    AFH_LAUNCH_CHECK("k2_lsf_gradient");
     return AFH_OK;
   };
   // every level in one launch (the box's spacing comes from its meta)
@@ -3375,7 +3168,7 @@ int32_t afh_mg_compute_phi_gradient(afh_mg *mg, int32_t i_fc, double fac, int32_
                          t->stream, t->ccv(mg->d.i_phi), t->fcv(i_fc),
                          i_norm ? t->ccv(i_norm) : nullptr, t->d_boxes, t->ids.at(1), t->nc,
                          t->bsz, t->fsz, fac);
-      H2_LAUNCH("k2_gradient");
+      AFH_LAUNCH_CHECK("k2_gradient");
     }
     return lsf_part();
   }
@@ -3386,7 +3179,7 @@ int32_t afh_mg_compute_phi_gradient(afh_mg *mg, int32_t i_fc, double fac, int32_
                        t->stream, t->ccv(mg->d.i_phi), t->fcv(i_fc),
                        i_norm ? t->ccv(i_norm) : nullptr, t->d_boxes, t->ids.at(l), t->nc,
                        t->bsz, t->fsz, fac);
-    H2_LAUNCH("k2_gradient");
+    AFH_LAUNCH_CHECK("k2_gradient");
   }
   return lsf_part();
 }
@@ -3410,11 +3203,11 @@ int32_t afh_mg_set_box_stencil(afh_mg *mg, int32_t id, const double *v,
                      "2-D: AFH_COARSE_DIRECT's basis does not diagonalise a level-1 grid "
                      "with electrode stencils; use AFH_COARSE_PFMG");
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  H2(hipStreamIsCapturing(t->stream, &cs));
+  AFH_HIP(hipStreamIsCapturing(t->stream, &cs));
   if (cs != hipStreamCaptureStatusNone)
     return set_error(AFH_ERR_STATE, "afh_mg_set_box_stencil during a graph capture");
   const size_t n2 = (size_t)t->nc * t->nc;
-  H2(hipStreamSynchronize(t->stream));
+  AFH_HIP(hipStreamSynchronize(t->stream));
   hipFree(mg->h_vp[id - 1]), hipFree(mg->h_bp[id - 1]);
   mg->h_vp[id - 1] = mg->h_bp[id - 1] = nullptr;
   mg->var_dirty = true;
@@ -3424,11 +3217,11 @@ int32_t afh_mg_set_box_stencil(afh_mg *mg, int32_t id, const double *v,
     else mg->h_vl1.erase(id);
   }
   if (!v) return AFH_OK;
-  H2(hipMalloc(&mg->h_vp[id - 1], sizeof(double) * 5 * n2));
-  H2(hipMemcpy(mg->h_vp[id - 1], v, sizeof(double) * 5 * n2, hipMemcpyHostToDevice));
+  AFH_HIP(hipMalloc(&mg->h_vp[id - 1], sizeof(double) * 5 * n2));
+  AFH_HIP(hipMemcpy(mg->h_vp[id - 1], v, sizeof(double) * 5 * n2, hipMemcpyHostToDevice));
   if (bc_correction) {
-    H2(hipMalloc(&mg->h_bp[id - 1], sizeof(double) * n2));
-    H2(hipMemcpy(mg->h_bp[id - 1], bc_correction, sizeof(double) * n2, hipMemcpyHostToDevice));
+    AFH_HIP(hipMalloc(&mg->h_bp[id - 1], sizeof(double) * n2));
+    AFH_HIP(hipMemcpy(mg->h_bp[id - 1], bc_correction, sizeof(double) * n2, hipMemcpyHostToDevice));
   }
   return AFH_OK;
 }
@@ -3451,22 +3244,22 @@ int32_t afh_mg_set_box_lsf(afh_mg *mg, int32_t id, int32_t n, const int32_t *ix,
       if (ix[q] < 1 || ix[q] > t->nc) return set_error(AFH_ERR_ARG, "cell index out of box");
   }
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  H2(hipStreamIsCapturing(t->stream, &cs));
+  AFH_HIP(hipStreamIsCapturing(t->stream, &cs));
   if (cs != hipStreamCaptureStatusNone)
     return set_error(AFH_ERR_STATE, "afh_mg_set_box_lsf during a graph capture");
   const size_t n2 = (size_t)t->nc * t->nc;
-  H2(hipStreamSynchronize(t->stream));
+  AFH_HIP(hipStreamSynchronize(t->stream));
   hipFree(mg->h_ix[id - 1]), hipFree(mg->h_dd[id - 1]), hipFree(mg->h_bv[id - 1]);
   mg->h_ix[id - 1] = nullptr, mg->h_dd[id - 1] = mg->h_bv[id - 1] = nullptr;
   mg->h_lsf_n[id - 1] = 0;
   mg->var_dirty = true;
   if (n == 0) return AFH_OK;
-  H2(hipMalloc(&mg->h_ix[id - 1], sizeof(int32_t) * 2 * n));
-  H2(hipMemcpy(mg->h_ix[id - 1], ix, sizeof(int32_t) * 2 * n, hipMemcpyHostToDevice));
-  H2(hipMalloc(&mg->h_dd[id - 1], sizeof(double) * 4 * n));
-  H2(hipMemcpy(mg->h_dd[id - 1], dd, sizeof(double) * 4 * n, hipMemcpyHostToDevice));
-  H2(hipMalloc(&mg->h_bv[id - 1], sizeof(double) * n2));
-  H2(hipMemcpy(mg->h_bv[id - 1], bval, sizeof(double) * n2, hipMemcpyHostToDevice));
+  AFH_HIP(hipMalloc(&mg->h_ix[id - 1], sizeof(int32_t) * 2 * n));
+  AFH_HIP(hipMemcpy(mg->h_ix[id - 1], ix, sizeof(int32_t) * 2 * n, hipMemcpyHostToDevice));
+  AFH_HIP(hipMalloc(&mg->h_dd[id - 1], sizeof(double) * 4 * n));
+  AFH_HIP(hipMemcpy(mg->h_dd[id - 1], dd, sizeof(double) * 4 * n, hipMemcpyHostToDevice));
+  AFH_HIP(hipMalloc(&mg->h_bv[id - 1], sizeof(double) * n2));
+  AFH_HIP(hipMemcpy(mg->h_bv[id - 1], bval, sizeof(double) * n2, hipMemcpyHostToDevice));
   mg->h_lsf_n[id - 1] = n;
   mg->i_lsf = i_lsf;
   return AFH_OK;
@@ -3504,35 +3297,25 @@ int32_t afh_fluid_create(afh_tree *t, const afh_fluid_desc *d, afh_fluid **out) 
       return set_error(AFH_ERR_UNSUPPORTED, "2-D: rate type %d", ty);
   }
   afh_fluid *f = new afh_fluid();
+  // (destroyed on every error return below)
+  std::unique_ptr<afh_fluid, int32_t (*)(afh_fluid *)> hold(f, afh_fluid_destroy);
   f->t = t;
   f->d = *d;
   t->coord_fixed = true;
   f->d.reactions = nullptr;
   const size_t ntd = (size_t)d->td.n_points * d->td.n_cols;
   const size_t nch = (size_t)d->chem.n_points * d->chem.n_cols;
-  H2(hipMalloc(&f->d_td, sizeof(double) * ntd));
-  H2(hipMemcpy(f->d_td, d->td.rows_cols, sizeof(double) * ntd, hipMemcpyHostToDevice));
+  AFH_HIP(hipMalloc(&f->d_td, sizeof(double) * ntd));
+  AFH_HIP(hipMemcpy(f->d_td, d->td.rows_cols, sizeof(double) * ntd, hipMemcpyHostToDevice));
   if (nch) {
-    H2(hipMalloc(&f->d_chem, sizeof(double) * nch));
-    H2(hipMemcpy(f->d_chem, d->chem.rows_cols, sizeof(double) * nch, hipMemcpyHostToDevice));
+    AFH_HIP(hipMalloc(&f->d_chem, sizeof(double) * nch));
+    AFH_HIP(hipMemcpy(f->d_chem, d->chem.rows_cols, sizeof(double) * nch, hipMemcpyHostToDevice));
   }
-  std::vector<DevReaction> R(std::max(1, d->n_reactions));
-  for (int r = 0; r < d->n_reactions; r++) {
-    const afh_reaction &a = d->reactions[r];
-    DevReaction &b = R[r];
-    b.rate_type = a.rate_type, b.table_col = a.table_col, b.n_in = a.n_in, b.n_out = a.n_out;
-    b.rate_factor = a.rate_factor;
-    for (int q = 0; q < 4; q++) {
-      b.c[q] = a.c[q], b.ix_in[q] = a.ix_in[q], b.ix_out[q] = a.ix_out[q];
-      b.mult_out[q] = a.mult_out[q];
-    }
-  }
-  H2(hipMalloc(&f->d_reac, sizeof(DevReaction) * R.size()));
-  H2(hipMemcpy(f->d_reac, R.data(), sizeof(DevReaction) * R.size(), hipMemcpyHostToDevice));
+  if (int32_t e = upload_reactions(d, [](int ix) { return ix; }, &f->d_reac)) return e;
   f->e_index = e_index;
   if (d->n_ions > 0)
-    H2(hipMalloc(&f->d_gc2, sizeof(double) * (size_t)(1 + d->n_ions) * t->nb * 4 * t->nc));
-  *out = f;
+    AFH_HIP(hipMalloc(&f->d_gc2, sizeof(double) * (size_t)(1 + d->n_ions) * t->nb * 4 * t->nc));
+  *out = hold.release();
   return AFH_OK;
 }
 
@@ -3541,7 +3324,7 @@ int32_t afh_fluid_destroy(afh_fluid *f) {
   hipStreamSynchronize(f->t->stream);
   hipFree(f->d_td), hipFree(f->d_chem), hipFree(f->d_reac);
   hipFree(f->d_ids), hipFree(f->d_mstat), hipFree(f->d_gc2), hipFree(f->d_sf_ion);
-  hipFree(f->d_rs_part), hipFree(f->d_rs_out);
+  f->rs.release();
   delete f;
   return AFH_OK;
 }
@@ -3571,7 +3354,7 @@ static int32_t set_rhs(afh_fluid *f, int32_t i_rhs, int32_t s_in, double *max_rh
     hipLaunchKernelGGL(k2_set_rhs, grid2(t->bsz, n), blk2(t->bsz), 0, t->stream, t->ccv(i_rhs), A,
                        t->leaves.at(l), t->nc, t->bsz,
                        max_rhs ? t->red + 3 * RED_SHARDS : nullptr);
-    H2_LAUNCH("k2_set_rhs");
+    AFH_LAUNCH_CHECK("k2_set_rhs");
   }
   return max_rhs ? red_read(t, 3, 1, 1, max_rhs) : AFH_OK;
 }
@@ -3626,7 +3409,7 @@ static int32_t flux_tree(afh_fluid *f, int32_t s_deriv, double *dt_lim, bool fet
     const int n = t->refb.n(l);
     if (!n) continue;
     restrict_boxes(t, t->ccv(iv), t->refb.at(l), n, true);
-    H2_LAUNCH("k2_restrict");
+    AFH_LAUNCH_CHECK("k2_restrict");
   }
   int32_t e;
   if ((e = red_init(t, 0, -HUGE_VAL, 2))) return e;  // CFL and conductivity maxima
@@ -3644,11 +3427,11 @@ static int32_t flux_tree(afh_fluid *f, int32_t s_deriv, double *dt_lim, bool fet
     if (!n) continue;
     hipLaunchKernelGGL(k2_gc2, grid2(4 * nc, n), blk2(4 * nc), 0, t->stream, t->ccv(iv), t->gc2,
                        t->d_boxes, t->leaves.at(l), nc, t->bsz, t->bc4(iv));
-    H2_LAUNCH("k2_gc2");
-    prof_mark(t, AFH_PROF_FLUX);
+    AFH_LAUNCH_CHECK("k2_gc2");
+    prof_begin(t, AFH_PROF_FLUX);
     hipLaunchKernelGGL(k2_flux, grid2(nc * nc, n), blk2(nc * nc), 0, t->stream, A,
                        t->leaves.at(l), t->d_boxes, nc, t->bsz, t->fsz, t->red);
-    H2_LAUNCH("k2_flux");
+    AFH_LAUNCH_CHECK("k2_flux");
     // ne and |E| read, two face fields read and two fluxes written per cell
     prof_end(t, AFH_PROF_FLUX, 48.0 * nc * nc * n);
   }
@@ -3657,11 +3440,11 @@ static int32_t flux_tree(afh_fluid *f, int32_t s_deriv, double *dt_lim, bool fet
   if (ntask && t->cyl()) {
     hipLaunchKernelGGL(k2_consistent_cyl, dim3((ntask * nc + NT - 1) / NT), dim3(NT), 0,
                        t->stream, t->fcv(f->d.f_flux), t->d_boxes, t->cflux.d, ntask, nc, t->fsz);
-    H2_LAUNCH("k2_consistent_cyl");
+    AFH_LAUNCH_CHECK("k2_consistent_cyl");
   } else if (ntask) {
     hipLaunchKernelGGL(k2_consistent, dim3((ntask * nc + NT - 1) / NT), dim3(NT), 0, t->stream,
                        t->fcv(f->d.f_flux), t->d_boxes, t->cflux.d, ntask, nc, t->fsz);
-    H2_LAUNCH("k2_consistent");
+    AFH_LAUNCH_CHECK("k2_consistent");
   }
   if (!fetch) return AFH_OK;
   double r[2];
@@ -3692,7 +3475,7 @@ static int32_t flux_tree_ions(afh_fluid *f, int32_t s_deriv, double *dt_lim, boo
     if (!n) continue;
     for (int q = 0; q < nsp; q++) {
       restrict_boxes(t, t->ccv(iv[q]), t->refb.at(l), n, true);
-      H2_LAUNCH("k2_restrict");
+      AFH_LAUNCH_CHECK("k2_restrict");
     }
   }
   int32_t e;
@@ -3723,9 +3506,9 @@ static int32_t flux_tree_ions(afh_fluid *f, int32_t s_deriv, double *dt_lim, boo
       hipLaunchKernelGGL(k2_gc2, grid2(4 * nc, n), blk2(4 * nc), 0, t->stream, t->ccv(iv[q]),
                          f->d_gc2 + q * gstride, t->d_boxes, t->leaves.at(l), nc, t->bsz,
                          t->bc4(iv[q]));
-      H2_LAUNCH("k2_gc2");
+      AFH_LAUNCH_CHECK("k2_gc2");
     }
-    prof_mark(t, AFH_PROF_FLUX);
+    prof_begin(t, AFH_PROF_FLUX);
     const dim3 g = grid2(nc * nc, n), bk = blk2(nc * nc);
     if (ni == 1)
       hipLaunchKernelGGL(k2_flux_ions<1>, g, bk, 0, t->stream, A, I, t->leaves.at(l), t->d_boxes,
@@ -3736,7 +3519,7 @@ static int32_t flux_tree_ions(afh_fluid *f, int32_t s_deriv, double *dt_lim, boo
     else
       hipLaunchKernelGGL(k2_flux_ions<0>, g, bk, 0, t->stream, A, I, t->leaves.at(l), t->d_boxes,
                          nc, t->bsz, t->fsz, t->red);
-    H2_LAUNCH("k2_flux_ions");
+    AFH_LAUNCH_CHECK("k2_flux_ions");
     // k2_flux's 48 B per cell, and per ion one density read and two fluxes written
     prof_end(t, AFH_PROF_FLUX, (48.0 + 24.0 * ni) * nc * nc * n);
   }
@@ -3749,7 +3532,7 @@ static int32_t flux_tree_ions(afh_fluid *f, int32_t s_deriv, double *dt_lim, boo
     else
       hipLaunchKernelGGL(k2_consistent, dim3((ntask * nc + NT - 1) / NT), dim3(NT), 0, t->stream,
                          t->fcv(fv[q]), t->d_boxes, t->cflux.d, ntask, nc, t->fsz);
-    H2_LAUNCH("k2_consistent");
+    AFH_LAUNCH_CHECK("k2_consistent");
   }
   if (!fetch) return AFH_OK;
   double r[2];
@@ -3760,22 +3543,9 @@ static int32_t flux_tree_ions(afh_fluid *f, int32_t s_deriv, double *dt_lim, boo
 
 // the partial rows of a last step with the rate sums on: one per update
 // workgroup of every leaf
-static int32_t rate_sums_reserve(afh_fluid *f) {
-  afh_tree *t = f->t;
-  const size_t rows = (size_t)(t->leaves.off[t->nlvl] - t->leaves.off[0]) *
-                      grid2(t->nc * t->nc, 1).x;
-  const size_t ncol = (size_t)f->d.n_reactions + 1;
-  if (!f->d_rs_out) H2(hipMalloc(&f->d_rs_out, ncol * sizeof(double)));
-  if (rows > f->rs_cap) {
-    // (a queued fold may still read the old rows)
-    H2(hipStreamSynchronize(t->stream));
-    hipFree(f->d_rs_part);
-    f->d_rs_part = nullptr;
-    f->rs_cap = 0;
-    H2(hipMalloc(&f->d_rs_part, rows * ncol * sizeof(double)));
-    f->rs_cap = rows;
-  }
-  return AFH_OK;
+static size_t rate_sum_rows(const afh_fluid *f) {
+  const afh_tree *t = f->t;
+  return (size_t)(t->leaves.off[t->nlvl] - t->leaves.off[0]) * grid2(t->nc * t->nc, 1).x;
 }
 
 // fetch = false: the chemistry minimum stays in slot 2 (last step)
@@ -3822,20 +3592,20 @@ static int32_t update(afh_fluid *f, double dt, int32_t s_deriv, int32_t n_prev,
       return set_error(AFH_ERR_UNSUPPORTED,
                        "2-D: the update mask in cylindrical coordinates is not built");
     // the leaves' mask summary from the level set as it is now
-    if (!f->d_mstat) H2(hipMalloc(&f->d_mstat, (size_t)t->nb));
+    if (!f->d_mstat) AFH_HIP(hipMalloc(&f->d_mstat, (size_t)t->nb));
     M.lsf = t->ccv(f->mask_iv), M.stat = f->d_mstat;
     const int nl = t->leaves.off[t->nlvl] - t->leaves.off[0];
     for (int c0 = 0; c0 < nl; c0 += 65535) {
       hipLaunchKernelGGL(k2_mask_status, dim3(std::min(65535, nl - c0)), dim3(64), 0, t->stream,
                          M.lsf, t->leaves.at(1) + c0, t->nc, t->bsz, f->d_mstat);
-      H2_LAUNCH("k2_mask_status");
+      AFH_LAUNCH_CHECK("k2_mask_status");
     }
   }
   // the rate sums (afh_fluid_set_rate_sums): last steps only
-  const bool rates = f->rs_on && A.last_step;
+  const bool rates = f->rs.on && A.last_step;
   const int upd_gx = (int)grid2(t->nc * t->nc, 1).x;
   if (rates)
-    if (int32_t e = rate_sums_reserve(f)) return e;
+    if (int32_t e = f->rs.reserve(rate_sum_rows(f), (size_t)A.nr + 1, t->stream)) return e;
   for (int l = 1; l <= t->nlvl; l++) {
     const int n = t->leaves.n(l);
     if (!n) continue;
@@ -3843,7 +3613,7 @@ static int32_t update(afh_fluid *f, double dt, int32_t s_deriv, int32_t n_prev,
     const dim3 bk = blk2(t->nc * t->nc);
     const int32_t *ids = t->leaves.at(l);
     unsigned long long *red = t->red + 2 * RED_SHARDS;
-    const RateSumArgs RS{f->d_rs_part, (t->leaves.off[l - 1] - t->leaves.off[0]) * upd_gx,
+    const RateSumArgs RS{f->rs.part, (t->leaves.off[l - 1] - t->leaves.off[0]) * upd_gx,
                          t->fcv(f->d.f_field)};
     // the argument blocks of the features (the launch takes those that are on)
     const bool photo = f->d.i_photo > 0, mask = M.lsf != nullptr, ions = f->d.n_ions > 0;
@@ -3886,14 +3656,14 @@ static int32_t update(afh_fluid *f, double dt, int32_t s_deriv, int32_t n_prev,
       else if (t->cyl()) kind(std::true_type{}, std::false_type{});
       else kind(std::false_type{}, std::false_type{});
     });
-    H2_LAUNCH("k2_update");
+    AFH_LAUNCH_CHECK("k2_update");
   }
   if (rates) {
     const int rows = (t->leaves.off[t->nlvl] - t->leaves.off[0]) * upd_gx;
-    hipLaunchKernelGGL(k2_rate_fold, dim3(A.nr + 1), dim3(NT), 0, t->stream, f->d_rs_part, rows,
-                       A.nr + 1, f->d_rs_out);
-    H2_LAUNCH("k2_rate_fold");
-    f->rs_valid = true;
+    hipLaunchKernelGGL(k2_rate_fold, dim3(A.nr + 1), dim3(NT), 0, t->stream, f->rs.part, rows,
+                       A.nr + 1, f->rs.out);
+    AFH_LAUNCH_CHECK("k2_rate_fold");
+    f->rs.valid = true;
   }
   dt_lim[0] = 1e100, dt_lim[1] = 1e100;
   if (A.last_step && fetch) return red_read(t, 2, 1, 0, dt_lim);
@@ -3927,15 +3697,15 @@ int32_t afh_electrode_species_bc(afh_fluid *f, int32_t i_lsf, int32_t i_1pos_ion
   if (n_ids > 65535) return set_error(AFH_ERR_UNSUPPORTED, "electrode_species_bc: %d boxes", n_ids);
   if (n_ids > f->ids_cap) {
     // the previous list may still be read by a queued launch
-    H2(hipStreamSynchronize(t->stream));
+    AFH_HIP(hipStreamSynchronize(t->stream));
     hipFree(f->d_ids);
     f->d_ids = nullptr;
     f->ids_cap = 0;
-    H2(hipMalloc(&f->d_ids, sizeof(int32_t) * n_ids));
+    AFH_HIP(hipMalloc(&f->d_ids, sizeof(int32_t) * n_ids));
     f->ids_cap = n_ids;
   }
   // pageable source: the copy is staged before the call returns
-  H2(hipMemcpyAsync(f->d_ids, ids, sizeof(int32_t) * n_ids, hipMemcpyHostToDevice, t->stream));
+  AFH_HIP(hipMemcpyAsync(f->d_ids, ids, sizeof(int32_t) * n_ids, hipMemcpyHostToDevice, t->stream));
   ElecBcArgs A;
   A.ns = f->d.n_species;
   for (int s = 0; s < A.ns; s++) A.sp[s] = t->ccv(f->d.species_iv[s]);
@@ -3945,7 +3715,7 @@ int32_t afh_electrode_species_bc(afh_fluid *f, int32_t i_lsf, int32_t i_1pos_ion
   A.neumann_zero = neumann_zero ? 1 : 0;
   hipLaunchKernelGGL(k2_electrode_bc, grid2(t->nc * t->nc, n_ids), blk2(t->nc * t->nc), 0,
                      t->stream, A, f->d_ids, t->nc, t->bsz);
-  H2_LAUNCH("k2_electrode_bc");
+  AFH_LAUNCH_CHECK("k2_electrode_bc");
   return AFH_OK;
 }
 
@@ -3959,72 +3729,19 @@ int32_t afh_fluid_set_update_mask(afh_fluid *f, int32_t i_lsf) {
 int32_t afh_fluid_set_source_factor(afh_fluid *f, int32_t mode, const uint8_t *ionization,
                                     double min_electrons_per_cell, int32_t i_srcfac) {
   if (!f) return set_error(AFH_ERR_ARG, "afh_fluid_set_source_factor: null");
-  afh_tree *t = f->t;
-  if (mode != AFH_SRCFAC_NONE && mode != AFH_SRCFAC_FLUX)
-    return set_error(AFH_ERR_ARG, "afh_fluid_set_source_factor: unknown mode %d", mode);
-  if (mode == AFH_SRCFAC_FLUX && !ionization)
-    return set_error(AFH_ERR_ARG, "afh_fluid_set_source_factor: no ionization flags");
-  if (i_srcfac < 0 || i_srcfac > t->nvc)
-    return set_error(AFH_ERR_ARG, "afh_fluid_set_source_factor: bad i_srcfac %d", i_srcfac);
-  // (the other states of the species: update(), with the states of the step)
-  bool used = i_srcfac > 0 && (i_srcfac == f->d.i_efld || i_srcfac == f->d.i_photo ||
-                               i_srcfac == f->d.i_gas_dens || i_srcfac == f->mask_iv);
-  for (int s = 0; s < f->d.n_species && i_srcfac > 0; s++)
-    used = used || i_srcfac == f->d.species_iv[s];
-  if (used)
-    return set_error(AFH_ERR_ARG,
-                     "afh_fluid_set_source_factor: i_srcfac %d is a variable the step uses",
-                     i_srcfac);
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  H2(hipStreamIsCapturing(t->stream, &cs));
-  if (cs != hipStreamCaptureStatusNone)
-    return set_error(AFH_ERR_STATE, "afh_fluid_set_source_factor during a graph capture");
-  if (mode == AFH_SRCFAC_FLUX && f->d.n_reactions > 0) {
-    // (a queued update may still read the previous flags)
-    H2(hipStreamSynchronize(t->stream));
-    if (!f->d_sf_ion) H2(hipMalloc(&f->d_sf_ion, (size_t)f->d.n_reactions));
-    std::vector<uint8_t> flags(f->d.n_reactions);
-    for (int r = 0; r < f->d.n_reactions; r++) flags[r] = ionization[r] ? 1 : 0;
-    H2(hipMemcpy(f->d_sf_ion, flags.data(), flags.size(), hipMemcpyHostToDevice));
-  }
-  f->sf_mode = mode;
-  f->sf_min_e = min_electrons_per_cell;
-  f->sf_iv = i_srcfac;
-  return AFH_OK;
+  return set_source_factor(f, mode, ionization, min_electrons_per_cell, i_srcfac, false);
 }
 
 // (the 2-D library has no sharded trees: AFH_ERR_UNSUPPORTED does not arise)
 int32_t afh_fluid_set_rate_sums(afh_fluid *f, int32_t on) {
   if (!f) return set_error(AFH_ERR_ARG, "afh_fluid_set_rate_sums: null");
-  afh_tree *t = f->t;
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  H2(hipStreamIsCapturing(t->stream, &cs));
-  if (cs != hipStreamCaptureStatusNone)
-    return set_error(AFH_ERR_STATE, "afh_fluid_set_rate_sums during a graph capture");
-  if (on && !f->rs_on) {
-    if (int32_t e = rate_sums_reserve(f)) return e;
-    f->rs_valid = false;
-  }
-  f->rs_on = on != 0;
-  return AFH_OK;
+  return f->rs.set(on != 0, rate_sum_rows(f), (size_t)f->d.n_reactions + 1, f->t->stream);
 }
 
 int32_t afh_fluid_fetch_rate_sums(afh_fluid *f, double *rates, double *jdote) {
   if (!f || !jdote || (!rates && f->d.n_reactions > 0))
     return set_error(AFH_ERR_ARG, "afh_fluid_fetch_rate_sums: null");
-  afh_tree *t = f->t;
-  if (!f->rs_on) return set_error(AFH_ERR_STATE, "afh_fluid_fetch_rate_sums: the sums are off");
-  if (!f->rs_valid)
-    return set_error(AFH_ERR_STATE,
-                     "afh_fluid_fetch_rate_sums: no last step since the sums were switched on");
-  const int nr = f->d.n_reactions;
-  std::vector<double> h(nr + 1);
-  H2(hipMemcpyAsync(h.data(), f->d_rs_out, (nr + 1) * sizeof(double), hipMemcpyDeviceToHost,
-                    t->stream));
-  H2(hipStreamSynchronize(t->stream));
-  for (int r = 0; r < nr; r++) rates[r] = h[r];
-  *jdote = h[nr];
-  return AFH_OK;
+  return f->rs.fetch(f->d.n_reactions, f->t->stream, rates, jdote);
 }
 
 int32_t afh_flux_upwind_tree(afh_fluid *f, int32_t s_deriv, double *dt_lim) {
@@ -4097,7 +3814,7 @@ int32_t afh_photoi_set_src(afh_fluid *f, int32_t i_rhs, int32_t alpha_col, doubl
                      t->ccv(i_rhs), t->ccv(f->d.i_efld), t->ccv(f->d.i_electron),
                      f->d.gas_number_density, dev_lt(f->d.td, f->d_td), alpha_col, coeff,
                      t->leaves.at(1), n, t->nc, t->bsz);
-  H2_LAUNCH("k2_photoi_src");
+  AFH_LAUNCH_CHECK("k2_photoi_src");
   return AFH_OK;
 }
 
@@ -4121,7 +3838,7 @@ int32_t afh_photoi_helmh_compute(afh_mg *const *modes, int32_t n_modes, const do
   const int src = modes[n_modes - 1]->d.i_rhs;
   for (int n = 0; n + 1 < n_modes; n++)
     if (modes[n]->d.i_rhs != src)
-      H2(hipMemcpyAsync(t->ccv(modes[n]->d.i_rhs), t->ccv(src), sizeof(double) * total,
+      AFH_HIP(hipMemcpyAsync(t->ccv(modes[n]->d.i_rhs), t->ccv(src), sizeof(double) * total,
                         hipMemcpyDeviceToDevice, t->stream));
   int32_t e;
   double max_rhs;
@@ -4142,8 +3859,8 @@ int32_t afh_photoi_helmh_compute(afh_mg *const *modes, int32_t n_modes, const do
     std::vector<uint8_t> leaf(t->nb, 0);
     for (const auto &lv : t->h_leaves)
       for (int id : lv) leaf[id - 1] = 1;
-    H2(hipMalloc(&t->d_leaf, t->nb));
-    H2(hipMemcpy(t->d_leaf, leaf.data(), t->nb, hipMemcpyHostToDevice));
+    AFH_HIP(hipMalloc(&t->d_leaf, t->nb));
+    AFH_HIP(hipMemcpy(t->d_leaf, leaf.data(), t->nb, hipMemcpyHostToDevice));
   }
   for (int n0 = 0; n0 < n_modes; n0 += 4) {
     SumArgs S;
@@ -4154,7 +3871,7 @@ int32_t afh_photoi_helmh_compute(afh_mg *const *modes, int32_t n_modes, const do
     }
     hipLaunchKernelGGL(k2_photoi_sum, dim3((unsigned)((total + NT - 1) / NT)), dim3(NT), 0,
                        t->stream, t->ccv(i_photo), S, t->d_leaf, t->bsz, total, n0 == 0);
-    H2_LAUNCH("k2_photoi_sum");
+    AFH_LAUNCH_CHECK("k2_photoi_sum");
   }
   return AFH_OK;
 }
@@ -4419,18 +4136,14 @@ __global__ void __launch_bounds__(NT)
   out[2 * q + 1] = -1.0;
 }
 
-static int32_t device_list(const std::vector<int32_t> &h, int32_t **d) {
-  H2(hipMalloc(d, sizeof(int32_t) * std::max<size_t>(1, h.size())));
-  if (!h.empty())
-    H2(hipMemcpy(*d, h.data(), sizeof(int32_t) * h.size(), hipMemcpyHostToDevice));
-  return AFH_OK;
-}
-
 static int32_t box_reduce(afh_tree *t, int iv, int op, int power, std::vector<double> &res) {
   const int nl = t->leaves.off[t->nlvl];
   res.assign(2 * (size_t)nl, 0.0);
   if (!nl) return AFH_OK;
-  if (!t->d_boxred) H2(hipMalloc(&t->d_boxred, sizeof(double) * 2 * t->nb));
+  if (!t->d_boxred) {
+    AFH_HIP(hipMalloc(&t->d_boxred, sizeof(double) * 2 * t->nb));
+    t->boxred_cap = t->nb;
+  }
   const dim3 grid((nl + NT - 1) / NT), blk(NT);
   const double *v = t->ccv(iv);
   switch (op) {
@@ -4454,10 +4167,10 @@ static int32_t box_reduce(afh_tree *t, int iv, int op, int power, std::vector<do
     hipLaunchKernelGGL(k2_box_reduce<AFH_RED_MAXABS>, grid, blk, 0, t->stream, v, t->leaves.d,
                        nl, t->nc, t->bsz, power, t->d_boxred);
   }
-  H2_LAUNCH("k2_box_reduce");
-  H2(hipMemcpyAsync(res.data(), t->d_boxred, sizeof(double) * 2 * nl, hipMemcpyDeviceToHost,
+  AFH_LAUNCH_CHECK("k2_box_reduce");
+  AFH_HIP(hipMemcpyAsync(res.data(), t->d_boxred, sizeof(double) * 2 * nl, hipMemcpyDeviceToHost,
                     t->stream));
-  H2(hipStreamSynchronize(t->stream));
+  AFH_HIP(hipStreamSynchronize(t->stream));
   return AFH_OK;
 }
 
@@ -4514,9 +4227,9 @@ int32_t afh_tree_regrid(afh_tree *o, const afh_tree_desc *d, afh_tree **out) {
     if ((e = device_list(rchild, &d_list))) return e;
     for (int iv : o->auto_vars) {
       restrict_boxes(o, o->ccv(iv), d_list, (int)rchild.size(), true);
-      H2_LAUNCH("k2_restrict");
+      AFH_LAUNCH_CHECK("k2_restrict");
     }
-    H2(hipStreamSynchronize(o->stream));
+    AFH_HIP(hipStreamSynchronize(o->stream));
     hipFree(d_list);
     d_list = nullptr;
   }
@@ -4531,14 +4244,14 @@ int32_t afh_tree_regrid(afh_tree *o, const afh_tree_desc *d, afh_tree **out) {
     hipLaunchKernelGGL(k2_copy_boxes, dim3((unsigned)((t->bsz + NT - 1) / NT), n, t->nvc),
                        dim3(NT), 0, t->stream, o->cc, t->cc, d_list, t->bsz,
                        (size_t)o->nb * o->bsz, (size_t)t->nb * t->bsz);
-    H2_LAUNCH("k2_copy_boxes");
+    AFH_LAUNCH_CHECK("k2_copy_boxes");
     if (t->nvf > 0) {
       hipLaunchKernelGGL(k2_copy_boxes, dim3((unsigned)((t->fsz + NT - 1) / NT), n, t->nvf),
                          dim3(NT), 0, t->stream, o->fc, t->fc, d_list, t->fsz,
                          (size_t)o->nb * o->fsz, (size_t)t->nb * t->fsz);
-      H2_LAUNCH("k2_copy_boxes");
+      AFH_LAUNCH_CHECK("k2_copy_boxes");
     }
-    H2(hipStreamSynchronize(t->stream));
+    AFH_HIP(hipStreamSynchronize(t->stream));
     hipFree(d_list);
     d_list = nullptr;
   }
@@ -4556,18 +4269,18 @@ int32_t afh_tree_regrid(afh_tree *o, const afh_tree_desc *d, afh_tree **out) {
                                                  : k2_prolong_new<AFH_PROLONG_LINEAR>;
       hipLaunchKernelGGL(kern, grid2(hn * hn, n), blk2(hn * hn), 0, t->stream, t->ccv(iv),
                          t->d_boxes, d_list, nc, t->bsz, m.prolong_lim);
-      H2_LAUNCH("k2_prolong_new");
+      AFH_LAUNCH_CHECK("k2_prolong_new");
     }
     // af_gc_box of every new box (sides, then corners) once all are prolonged
     for (int iv : t->auto_vars) {
       hipLaunchKernelGGL(k2_gc, grid2(4 * nc, n), blk2(4 * nc), 0, t->stream, t->ccv(iv),
                          t->d_boxes, d_list, nc, t->bsz, t->bc4(iv));
-      H2_LAUNCH("k2_gc");
+      AFH_LAUNCH_CHECK("k2_gc");
       hipLaunchKernelGGL(k2_corners, dim3((4 * n + NT - 1) / NT), dim3(NT), 0, t->stream,
                          t->ccv(iv), t->d_boxes, d_list, n, nc, t->bsz);
-      H2_LAUNCH("k2_corners");
+      AFH_LAUNCH_CHECK("k2_corners");
     }
-    H2(hipStreamSynchronize(t->stream));
+    AFH_HIP(hipStreamSynchronize(t->stream));
     hipFree(d_list);
     d_list = nullptr;
   }
@@ -4588,14 +4301,14 @@ int32_t afh_refine_flags(afh_fluid *f, const afh_refine_desc *d, const uint8_t *
   const int nb = t->nb, nids = t->ids.off[t->nlvl];
   int32_t *d_flags = nullptr;
   uint32_t *d_masks = nullptr;
-  H2(hipMalloc(&d_flags, sizeof(int32_t) * nb));
-  H2(hipMalloc(&d_masks, sizeof(uint32_t) * nb));
-  H2(hipMemsetAsync(d_flags, 0, sizeof(int32_t) * nb, t->stream));
-  H2(hipMemsetAsync(d_masks, 0, sizeof(uint32_t) * nb, t->stream));
+  AFH_HIP(hipMalloc(&d_flags, sizeof(int32_t) * nb));
+  AFH_HIP(hipMalloc(&d_masks, sizeof(uint32_t) * nb));
+  AFH_HIP(hipMemsetAsync(d_flags, 0, sizeof(int32_t) * nb, t->stream));
+  AFH_HIP(hipMemsetAsync(d_masks, 0, sizeof(uint32_t) * nb, t->stream));
   uint8_t *d_elec = nullptr;
   if (electrode_box) {
-    H2(hipMalloc(&d_elec, nb));
-    H2(hipMemcpyAsync(d_elec, electrode_box, nb, hipMemcpyHostToDevice, t->stream));
+    AFH_HIP(hipMalloc(&d_elec, nb));
+    AFH_HIP(hipMemcpyAsync(d_elec, electrode_box, nb, hipMemcpyHostToDevice, t->stream));
   }
   RefineArgs2 A;
   A.elec = d_elec;
@@ -4607,92 +4320,43 @@ int32_t afh_refine_flags(afh_fluid *f, const afh_refine_desc *d, const uint8_t *
   if (nids > 0) {
     hipLaunchKernelGGL(k2_refine_flags, dim3(nids), dim3(NT), 0, t->stream, A, t->d_boxes,
                        t->ids.d, t->nc, t->bsz, d_flags, d_masks);
-    H2_LAUNCH("k2_refine_flags");
+    AFH_LAUNCH_CHECK("k2_refine_flags");
   }
-  H2(hipMemcpyAsync(flags, d_flags, sizeof(int32_t) * nb, hipMemcpyDeviceToHost, t->stream));
-  H2(hipMemcpyAsync(masks, d_masks, sizeof(uint32_t) * nb, hipMemcpyDeviceToHost, t->stream));
-  H2(hipStreamSynchronize(t->stream));
+  AFH_HIP(hipMemcpyAsync(flags, d_flags, sizeof(int32_t) * nb, hipMemcpyDeviceToHost, t->stream));
+  AFH_HIP(hipMemcpyAsync(masks, d_masks, sizeof(uint32_t) * nb, hipMemcpyDeviceToHost, t->stream));
+  AFH_HIP(hipStreamSynchronize(t->stream));
   hipFree(d_flags), hipFree(d_masks), hipFree(d_elec);
   return AFH_OK;
 }
 
-// The reductions of afivo_hip_analysis.h (kernels and launchers:
-// afh_analysis_dev.h) with the 2-D shapes: loc = (id, i, j, 0), r0 and r1 read
-// to their second entry, coord_val 3 x n_max. (No tree of this library is
-// sharded.) The launchers' view of the tree, with the per-leaf scratch and the
-// result buffer (4 + n_list doubles) grown to fit.
+// The reductions of afivo_hip_analysis.h (kernels, launchers and the bodies of
+// the entry points: afh_analysis_dev.h) with the 2-D shapes. (No tree of this
+// library is sharded.)
 #define AN2_TREE(t, what) \
   if (!(t)) return set_error(AFH_ERR_ARG, "%s: null tree", what)
-static int32_t an_ctx(afh_tree *t, size_t n_list, const char *what, afh_an::Ctx &c) {
-  const int nl = t->leaves.off[t->nlvl];
-  if (!t->d_boxred) H2(hipMalloc(&t->d_boxred, sizeof(double) * 2 * t->nb));
-  if (4 + n_list > t->an_cap) {
-    H2(hipStreamSynchronize(t->stream));
-    hipFree(t->d_an);
-    t->d_an = nullptr, t->an_cap = 0;
-    H2(hipMalloc(&t->d_an, sizeof(double) * (4 + n_list)));
-    t->an_cap = 4 + n_list;
-  }
-  c.stream = t->stream;
-  c.nd = 2, c.nc = t->nc, c.nl = nl;
-  c.leaves = t->leaves.d;
-  c.meta = t->d_boxes;
-  c.part = t->d_boxred, c.res = t->d_an;
-  return AFH_OK;
-}
 
 int32_t afh_tree_reduce_fc(afh_tree *t, int32_t ivf, int32_t dim, int32_t op, double *out,
                            int32_t *loc) {
   AN2_TREE(t, "afh_tree_reduce_fc");
-  if (ivf < 1 || ivf > t->nvf || dim < 1 || dim > 2 || !out ||
-      (op != AFH_RED_MAX && op != AFH_RED_MIN))
-    return set_error(AFH_ERR_ARG, "afh_tree_reduce_fc: bad argument");
-  afh_an::Ctx c;
-  if (int32_t e = an_ctx(t, 0, "afh_tree_reduce_fc", c)) return e;
-  const bool is_min = op == AFH_RED_MIN;
-  afh_an::Region none = {};
-  H2(afh_an::best_loc(c, t->fcv(ivf), afh_an::geo_fc(2, t->nc, t->fsz, dim - 1), is_min,
-                           none, (is_min ? 1 : -1) * (1.7976931348623157e308 / 10), out, loc));
-  return AFH_OK;
+  return afh_an::reduce_fc<2>(t, ivf, dim, op, out, loc);
 }
 
 int32_t afh_tree_zminmax_threshold(afh_tree *t, int32_t iv, double threshold,
                                    const double *limits, double *out) {
   AN2_TREE(t, "afh_tree_zminmax_threshold");
-  if (iv < 1 || iv > t->nvc || !limits || !out)
-    return set_error(AFH_ERR_ARG, "afh_tree_zminmax_threshold: bad argument");
-  afh_an::Ctx c;
-  if (int32_t e = an_ctx(t, 0, "afh_tree_zminmax_threshold", c)) return e;
-  H2(afh_an::zminmax(c, t->ccv(iv), afh_an::geo_cc(2, t->nc, t->bsz), threshold, limits,
-                          out));
-  return AFH_OK;
+  return afh_an::zminmax_threshold<2>(t, iv, threshold, limits, out);
 }
 
 int32_t afh_tree_max_region(afh_tree *t, int32_t iv, const double *r0, const double *r1,
                             double *out, int32_t *loc) {
   AN2_TREE(t, "afh_tree_max_region");
-  if (iv < 1 || iv > t->nvc || !r0 || !r1 || !out)
-    return set_error(AFH_ERR_ARG, "afh_tree_max_region: bad argument");
-  afh_an::Ctx c;
-  if (int32_t e = an_ctx(t, 0, "afh_tree_max_region", c)) return e;
-  afh_an::Region R = {};
-  R.on = 1;
-  for (int d = 0; d < 2; d++) R.r0[d] = r0[d], R.r1[d] = r1[d];
-  H2(afh_an::best_loc(c, t->ccv(iv), afh_an::geo_cc(2, t->nc, t->bsz), false, R, -1e100,
-                           out, loc));
-  return AFH_OK;
+  return afh_an::max_region<2>(t, iv, r0, r1, out, loc);
 }
 
 int32_t afh_tree_local_maxima(afh_tree *t, int32_t iv, double threshold, int32_t n_max,
                               double *coord_val, int32_t *n_found) {
   AN2_TREE(t, "afh_tree_local_maxima");
-  if (iv < 1 || iv > t->nvc || n_max < 0 || (n_max > 0 && !coord_val) || !n_found)
-    return set_error(AFH_ERR_ARG, "afh_tree_local_maxima: bad argument");
-  afh_an::Ctx c;
-  if (int32_t e = an_ctx(t, (size_t)3 * n_max, "afh_tree_local_maxima", c)) return e;
-  H2(afh_an::maxima(c, t->ccv(iv), afh_an::geo_cc(2, t->nc, t->bsz), threshold, n_max,
-                         coord_val, n_found));
-  return AFH_OK;
+  return afh_an::local_maxima<2>(t, iv, threshold, n_max, coord_val, n_found);
 }
 
 // af_tree_sum_cc (m_af_utils.f90:966-1026): per leaf the sum of cc**power
@@ -4704,13 +4368,9 @@ int32_t afh_tree_sum_cc(afh_tree *t, int32_t iv, int32_t power, double *out) {
   if (power < 1 || !out) return set_error(AFH_ERR_ARG, "afh_tree_sum_cc: bad argument");
   std::vector<double> res;
   if (int32_t e = box_reduce(t, iv, 0, power, res)) return e;
-  double sum = 0.0;
-  size_t q = 0;
-  for (int l = 1; l <= t->nlvl; l++) {
-    const double fac = t->lvl_dr[2 * (l - 1)] * t->lvl_dr[2 * (l - 1) + 1];
-    for (int b = 0; b < t->leaves.n(l); b++, q++) sum = sum + fac * res[2 * q];
-  }
-  *out = sum;
+  std::vector<double> fac(t->nlvl);
+  for (int l = 0; l < t->nlvl; l++) fac[l] = t->lvl_dr[2 * l] * t->lvl_dr[2 * l + 1];
+  *out = fold_leaf_sums(res, fac, t->h_leaves);
   return AFH_OK;
 }
 
@@ -4723,21 +4383,8 @@ int32_t afh_tree_reduce_loc(afh_tree *t, int32_t iv, int32_t op, double *out, in
     return set_error(AFH_ERR_ARG, "afh_tree_reduce_loc: bad argument");
   std::vector<double> res;
   if (int32_t e = box_reduce(t, iv, op, 1, res)) return e;
-  const bool is_min = op == AFH_RED_MIN;
-  double val = (is_min ? 1 : -1) * (1.7976931348623157e308 / 10);
-  int32_t lid = -1, lix = -1;
-  size_t q = 0;
-  for (int l = 1; l <= t->nlvl; l++)
-    for (int b = 0; b < t->leaves.n(l); b++, q++) {
-      const double tmp = res[2 * q];
-      const double nv = is_min ? std::min(tmp, val) : std::max(tmp, val);
-      if (std::fabs(nv - val) > 0) {
-        val = tmp;
-        lid = t->h_leaves[l - 1][b];
-        lix = (int32_t)res[2 * q + 1];
-      }
-    }
-  *out = val;
+  int32_t lid, lix;
+  *out = fold_leaf_best(res, t->h_leaves, op == AFH_RED_MIN, lid, lix);
   if (loc) {
     const int nc = t->nc;
     loc[0] = lid;

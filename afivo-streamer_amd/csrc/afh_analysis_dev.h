@@ -20,6 +20,7 @@
 #include <stdint.h>
 
 #include "../../include/afivo_hip.h"
+#include "afh_common.h"
 
 namespace afh_an {
 namespace {
@@ -404,6 +405,95 @@ inline hipError_t maxima(const Ctx &c, const double *v, const Geo &g, double thr
   }
   delete[] h;
   return e;
+}
+
+// ---------------------------------------------------------- the entry points
+// The four functions of afivo_hip_analysis.h on a tree of either library (ND
+// = 3 or 2), after the library's guard of the handle. The 2-D shapes: loc =
+// (id, i, j, 0), r0 and r1 read to their second entry, coord_val 3 x n_max.
+//
+// The launchers' view of the tree, with the per-leaf scratch and the result
+// buffer (4 + n_list doubles) grown to fit.
+template <int ND, class Tree>
+inline int32_t an_ctx(Tree *t, size_t n_list, const char *what, Ctx &c) {
+  using afhc::set_error;
+  if constexpr (ND == 3)
+    if (t->hook || t->dev_reduce)
+      return set_error(AFH_ERR_UNSUPPORTED, "%s: the fold over the ranks of a sharded tree is "
+                       "not built", what);
+  const int nl = t->leaves.off[t->nlvl];
+  if (nl > t->boxred_cap) {
+    AFH_HIP(hipStreamSynchronize(t->stream));
+    hipFree(t->d_boxred);
+    t->d_boxred = nullptr, t->boxred_cap = 0;
+    AFH_HIP(hipMalloc(&t->d_boxred, sizeof(double) * 2 * nl));
+    t->boxred_cap = nl;
+  }
+  if (4 + n_list > t->an_cap) {
+    AFH_HIP(hipStreamSynchronize(t->stream));
+    hipFree(t->d_an);
+    t->d_an = nullptr, t->an_cap = 0;
+    AFH_HIP(hipMalloc(&t->d_an, sizeof(double) * (4 + n_list)));
+    t->an_cap = 4 + n_list;
+  }
+  c.stream = t->stream;
+  c.nd = ND, c.nc = t->nc, c.nl = nl;
+  c.leaves = t->leaves.d;
+  c.meta = t->d_boxes;
+  c.part = t->d_boxred, c.res = t->d_an;
+  return AFH_OK;
+}
+
+template <int ND, class Tree>
+inline int32_t reduce_fc(Tree *t, int32_t ivf, int32_t dim, int32_t op, double *out,
+                         int32_t *loc) {
+  if (ivf < 1 || ivf > t->nvf || dim < 1 || dim > ND || !out ||
+      (op != AFH_RED_MAX && op != AFH_RED_MIN))
+    return afhc::set_error(AFH_ERR_ARG, "afh_tree_reduce_fc: bad argument");
+  Ctx c;
+  if (int32_t e = an_ctx<ND>(t, 0, "afh_tree_reduce_fc", c)) return e;
+  const bool is_min = op == AFH_RED_MIN;
+  Region none = {};
+  AFH_HIP(best_loc(c, t->fcv(ivf), geo_fc(ND, t->nc, t->fsz, dim - 1), is_min, none,
+                   (is_min ? 1 : -1) * (DBL_MAX / 10), out, loc));
+  return AFH_OK;
+}
+
+template <int ND, class Tree>
+inline int32_t zminmax_threshold(Tree *t, int32_t iv, double threshold, const double *limits,
+                                 double *out) {
+  if (iv < 1 || iv > t->nvc || !limits || !out)
+    return afhc::set_error(AFH_ERR_ARG, "afh_tree_zminmax_threshold: bad argument");
+  Ctx c;
+  if (int32_t e = an_ctx<ND>(t, 0, "afh_tree_zminmax_threshold", c)) return e;
+  AFH_HIP(zminmax(c, t->ccv(iv), geo_cc(ND, t->nc, t->bsz), threshold, limits, out));
+  return AFH_OK;
+}
+
+template <int ND, class Tree>
+inline int32_t max_region(Tree *t, int32_t iv, const double *r0, const double *r1, double *out,
+                          int32_t *loc) {
+  if (iv < 1 || iv > t->nvc || !r0 || !r1 || !out)
+    return afhc::set_error(AFH_ERR_ARG, "afh_tree_max_region: bad argument");
+  Ctx c;
+  if (int32_t e = an_ctx<ND>(t, 0, "afh_tree_max_region", c)) return e;
+  Region R = {};
+  R.on = 1;
+  for (int d = 0; d < ND; d++) R.r0[d] = r0[d], R.r1[d] = r1[d];
+  AFH_HIP(best_loc(c, t->ccv(iv), geo_cc(ND, t->nc, t->bsz), false, R, -1e100, out, loc));
+  return AFH_OK;
+}
+
+template <int ND, class Tree>
+inline int32_t local_maxima(Tree *t, int32_t iv, double threshold, int32_t n_max,
+                            double *coord_val, int32_t *n_found) {
+  if (iv < 1 || iv > t->nvc || n_max < 0 || (n_max > 0 && !coord_val) || !n_found)
+    return afhc::set_error(AFH_ERR_ARG, "afh_tree_local_maxima: bad argument");
+  Ctx c;
+  if (int32_t e = an_ctx<ND>(t, (size_t)(ND + 1) * n_max, "afh_tree_local_maxima", c)) return e;
+  AFH_HIP(maxima(c, t->ccv(iv), geo_cc(ND, t->nc, t->bsz), threshold, n_max, coord_val,
+                 n_found));
+  return AFH_OK;
 }
 
 }  // namespace

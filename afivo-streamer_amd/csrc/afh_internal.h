@@ -1,4 +1,8 @@
 // Internal declarations shared by the HIP translation units of libafivo_hip.
+// What does not depend on the dimension (error text, AFH_HIP, level lists,
+// kernel timing, limiter, lookup tables, reactions, ordered keys, ...) is in
+// afh_common.h, shared with libafivo_hip_2d; its names are visible in
+// namespace afh.
 //
 // Device layout (HBM):
 //   cc pool  [iv][box][k][j][i], (nc+2)^3 doubles per box, i fastest: each
@@ -23,26 +27,16 @@
 #include <utility>
 
 #include "../../include/afivo_hip.h"
+#include "afh_common.h"
 
 namespace afh {
 
-int32_t set_error(int32_t code, const char *fmt, ...);
-int32_t check_hip(hipError_t e, const char *what);
+using namespace afhc;
+
 // Data pools (cc, fc, gc2, the spare image). (Round 4's placement
 // experiments -- contiguous allocations, padding between variables, an
 // offset spare image -- changed nothing measurable and were removed.)
 int32_t pool_alloc(void **p, size_t bytes, const char *what);
-#define AFH_HIP(call)                                                         \
-  do {                                                                        \
-    hipError_t _e = (call);                                                   \
-    if (_e != hipSuccess) return ::afh::check_hip(_e, #call);                 \
-  } while (0)
-#define AFH_LAUNCH_CHECK(what)                                                \
-  do {                                                                        \
-    hipError_t _e = hipGetLastError();                                        \
-    if (_e != hipSuccess) return ::afh::check_hip(_e, what);                  \
-  } while (0)
-
 struct CcMethod {
   int set = 0;
   afh_bc bc[6];
@@ -57,13 +51,6 @@ struct GcArgs {
   afh_bc bc[6];
   int rb;
   int lim;
-};
-
-struct LevelList {
-  std::vector<int32_t> off;  // highest_lvl + 1 offsets
-  int32_t *d = nullptr;      // device, concatenated 1-based ids
-  int n(int lvl) const { return off[lvl] - off[lvl - 1]; }
-  const int32_t *at(int lvl) const { return d + off[lvl - 1]; }
 };
 
 }  // namespace afh
@@ -81,15 +68,15 @@ struct afh_tree {
   double r_base[3], dr_base[3];
   std::vector<afh_box_meta> boxes;  // host copy
   afh_box_meta *d_boxes = nullptr;
-  afh::LevelList ids, leaves, parents;
+  afhc::LevelList ids, leaves, parents;
   std::vector<std::vector<int32_t>> h_ids, h_leaves, h_parents;
   // leaves next to a refinement boundary, per level (af_restrict_ref_boundary)
-  afh::LevelList refb;
+  afhc::LevelList refb;
   // boxes with a refinement boundary on an x face, per level: the fills
   // without x faces (gc_lvl_var xfree) still fill theirs
-  afh::LevelList xrb;
+  afhc::LevelList xrb;
   // (parent id, nb) tasks of af_consistent_fluxes, per level
-  afh::LevelList cflux;
+  afhc::LevelList cflux;
   // af_consistent_fluxes has a task anywhere in the whole topology (all
   // ranks): the fused forward-Euler kernel needs every face flux final
   bool any_cflux = false;
@@ -113,11 +100,7 @@ struct afh_tree {
   std::vector<int> lvl_rb_coarse;
   bool own_stream = true;
   // kernel timing (afh_profile_*)
-  int prof_class = 0;
-  std::vector<hipEvent_t> ev_pool;
-  size_t ev_used = 0;
-  double prof_bytes = 0;
-  int64_t prof_launches = 0;
+  afhc::Prof prof;
   // box sharding (afh_tree_set_hook, afh_plan_*): exchange hook, the
   // smoother's spare phi image (variable 0 in hooks and plans), plans
   afh_hook_fn hook = nullptr;
@@ -208,13 +191,6 @@ struct afh_tree {
 
 namespace afh {
 // entry-point guard: a null or retired tree handle is an error
-// Workgroup lanes for a per-box launch of `work` items: the work rounded up
-// to whole waves, at most 256 (an 8^3 box's 64-cell face or 96 edge cells
-// without the idle waves of a 256-lane workgroup).
-inline int fit_blk(int work) {
-  return work < 256 ? ((work + 63) / 64) * 64 : 256;
-}
-
 // hipFuncAttributeMaxDynamicSharedMemorySize is per kernel (and device), not
 // per object: several multigrids in one process each need their own LDS size,
 // so the limit is only ever raised
@@ -244,16 +220,6 @@ inline int32_t live(const afh_tree *t, const char *what) {
     int32_t _e = ::afh::live((t), (what));                                     \
     if (_e) return _e;                                                        \
   } while (0)
-// per-level id lists -> one device array with offsets (frees L's old array)
-int32_t upload_list(afh_tree *t, LevelList &L,
-                    const std::vector<std::vector<int32_t>> &lists);
-// Kernel timing: bracket one launch of class `kc` (no-op unless enabled).
-void prof_begin(afh_tree *t, int kc);
-void prof_end(afh_tree *t, int kc, double bytes);
-// or: a start / end event pair for a launch that records them itself
-// (hipExtLaunchKernelGGL; false: class not timed), then prof_count
-bool prof_ext(afh_tree *t, int kc, hipEvent_t &e0, hipEvent_t &e1);
-void prof_count(afh_tree *t, double bytes);
 // Host launchers shared between translation units (afh_tree.hip).
 int32_t gc_lvl(afh_tree *t, int lvl, int iv, int corners, bool rims = false, int depth = 2);
 // ghost fill of level lvl of variable iv (0: the spare phi image), with the
@@ -303,11 +269,6 @@ __device__ __forceinline__ int red_shard() {
   return (int)((blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z)) &
                (RED_SHARDS - 1));
 }
-// Orderable encoding of doubles for atomicMax/Min on 64-bit integers.
-__device__ __forceinline__ unsigned long long dbl_to_ord(double x) {
-  unsigned long long u = __double_as_longlong(x);
-  return (u & 0x8000000000000000ull) ? ~u : (u | 0x8000000000000000ull);
-}
 // Fold a per-thread max into shard red_shard() of `red` (one atomic per
 // workgroup; blockDim.x a multiple of 64, at most 1024). Every thread calls.
 __device__ __forceinline__ void block_max_to_shard(double v,
@@ -322,19 +283,6 @@ __device__ __forceinline__ void block_max_to_shard(double v,
     atomicMax(&red[red_shard()], dbl_to_ord(v));
   }
 }
-inline double ord_to_dbl(unsigned long long o) {
-  unsigned long long u =
-      (o & 0x8000000000000000ull) ? (o & ~0x8000000000000000ull) : ~o;
-  double d;
-  memcpy(&d, &u, sizeof d);
-  return d;
-}
-inline unsigned long long host_dbl_to_ord(double x) {
-  unsigned long long u;
-  memcpy(&u, &x, sizeof u);
-  return (u & 0x8000000000000000ull) ? ~u : (u | 0x8000000000000000ull);
-}
-
 // A store of a kernel's output, streaming (nontemporal: no reuse expected
 // before eviction) when NT. The big per-level outputs are read back only by
 // the next kernel, from HBM anyway (a leaf level is GBs, the L2 + MALL a few
@@ -384,38 +332,6 @@ __device__ __forceinline__ Blk xcd_block() {
 
 __device__ __forceinline__ size_t ix3(int ng, int i, int j, int k) {
   return ((size_t)k * ng + j) * ng + i;
-}
-
-// af_limiter_apply (m_af_limiters.f90:41-149)
-__device__ __forceinline__ double limiter(int lim, double a, double b) {
-  const double third = 1 / 3.0;
-  switch (lim) {
-  case AFH_LIM_KOREN: {
-    const double aa = a * a, ab = a * b;
-    if (ab <= 0) return 0;
-    if (aa <= 0.25 * ab) return 2 * a;
-    if (aa <= 2.5 * ab) return third * (b + 2 * a);
-    return 2 * b;
-  }
-  case AFH_LIM_VANLEER: {
-    const double ab = a * b;
-    return ab > 0 ? 2 * ab / (a + b) : 0;
-  }
-  case AFH_LIM_NONE: return 0.5 * (a + b);
-  case AFH_LIM_ZERO: return 0.0;
-  default: {
-    const double th =
-        lim == AFH_LIM_MINMOD ? 1.0 : lim == AFH_LIM_MC ? 2.0 : 4 / 3.0;
-    if (a * b > 0) {
-      double m = fabs(th * a);
-      const double y = fabs(th * b), z = fabs(0.5 * (a + b));
-      if (y < m) m = y;
-      if (z < m) m = z;
-      return copysign(m, a);
-    }
-    return 0.0;
-  }
-  }
 }
 
 // Linear index t -> (i, j, k), 1-based, of an n x n x n block, i fastest.

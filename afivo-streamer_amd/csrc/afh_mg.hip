@@ -3266,7 +3266,7 @@ static int32_t prepare_var(afh_mg *mg) {
     for (int l = 0; l < nl; l++)
       for (int32_t id : src[l]) (mg->h_vp[id - 1] ? lv : lc)[l].push_back(id);
     int32_t e2;
-    if ((e2 = upload_list(t, c, lc)) || (e2 = upload_list(t, v, lv))) return e2;
+    if ((e2 = upload_list(c, lc)) || (e2 = upload_list(v, lv))) return e2;
     return AFH_OK;
   };
   if ((e = split(t->h_ids, mg->ids_c, mg->ids_v)) ||
@@ -3277,7 +3277,7 @@ static int32_t prepare_var(afh_mg *mg) {
   for (int l = 0; l < nl; l++)
     for (int32_t id : t->h_leaves[l])
       if (mg->h_lsf_n[id - 1]) ll[l].push_back(id);
-  return upload_list(t, mg->lsf_leaves, ll);
+  return upload_list(mg->lsf_leaves, ll);
 }
 
 static int32_t gsrb_half(afh_mg *mg, int lvl, int n, bool corners) {
@@ -4313,7 +4313,7 @@ static int32_t vcycle_graph(afh_mg *mg, int32_t set_residual, int max_lvl, bool 
   done = false;
   // (the multi-launch coarse cycles with a stopping rule read the device
   // every cycle too)
-  if (!mg->use_graphs || (t->hook && !mg->seg_graphs) || t->prof_class ||
+  if (!mg->use_graphs || (t->hook && !mg->seg_graphs) || t->prof.cls ||
       (mg->d.coarse_mode != AFH_COARSE_PFMG && mg->any_var && mg->lvl_var[0] &&
        !cs_electrode_fused(mg) && !mg->csd_ok) ||
       (mg->d.coarse_mode == AFH_COARSE_CYCLES && mg->d.coarse_tol > 0 && mg->small_from > 0))

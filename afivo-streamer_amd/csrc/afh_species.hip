@@ -21,6 +21,7 @@
 //                   sum_global_JdotE (665-731, afh_fluid_set_rate_sums)
 //   k_rate_fold     the workgroups' rate and J.E rows added in a fixed order
 #include <algorithm>
+#include <memory>
 #include <type_traits>
 #include <utility>
 
@@ -39,31 +40,11 @@ __device__ __forceinline__ size_t fidx(int nf, int d, int i, int j, int k) {
          (i - 1);
 }
 
-struct DevLT {
-  int n_points, n_cols;
-  double x_min, inv_fac;
-  const double *rc;
+// A lookup table as this library's kernels take it: the chemistry table also
+// carries a row-major copy for lt_at_rm (null in every other table)
+struct DevLTrm : DevLT {
   const double *rm = nullptr;  // row-major copy [row][col] (chemistry table)
 };
-
-// LT_get_loc + LT_get_col_at_loc (m_lookup_table.f90:330-406)
-__device__ __forceinline__ double lt_col(const DevLT &lt, int col, double x) {
-  const double frac = (x - lt.x_min) * lt.inv_fac;
-  int low;
-  double lf;
-  if (frac <= 0) {
-    low = 1;
-    lf = 1;
-  } else if (frac >= lt.n_points - 1) {
-    low = lt.n_points - 1;
-    lf = 0;
-  } else {
-    low = (int)ceil(frac);
-    lf = low - frac;
-  }
-  const double *r = lt.rc + (size_t)(col - 1) * lt.n_points;
-  return lf * r[low - 1] + (1 - lf) * r[low];
-}
 
 // limiter with a compile-time choice (LIM = AFH_LIM_KOREN, the reference's
 // flux limiter) or the runtime switch (LIM = 0)
@@ -248,7 +229,7 @@ struct FluxArgs {
   // k_flux_ion, which folds the maximum of the sum (null: folded here)
   double *sig;
   const double *gc2;
-  DevLT td;
+  DevLTrm td;
   double N_inv;
   // variable gas density (cc variable, ghost cells filled) or null: then
   // N_inv = 2 / (N_{f-1} + N_f) per face (src/m_fluid.f90:146-154);
@@ -263,7 +244,7 @@ struct FluxArgs {
 
 // LT_get_col(td_tbl, td_mobility/td_diffusion, x): both columns at the same
 // location (src/m_fluid.f90:168-174, m_lookup_table.f90:330-406)
-__device__ __forceinline__ void lt_mu_dc(const DevLT &lt, double x, double &mu,
+__device__ __forceinline__ void lt_mu_dc(const DevLTrm &lt, double x, double &mu,
                                          double &dc) {
   const double frac = (x - lt.x_min) * lt.inv_fac;
   int low;
@@ -325,7 +306,7 @@ __device__ __forceinline__ void face_vd(const FluxArgs &A, double Elo,
 // z it is recomputed (transport only, bitwise identical expression).
 // Table location of LT_get_loc (m_lookup_table.f90:330-363): row `low`
 // (1-based) and weight `lf` of that row.
-__device__ __forceinline__ void lt_loc(const DevLT &lt, double x, int &low,
+__device__ __forceinline__ void lt_loc(const DevLTrm &lt, double x, int &low,
                                        double &lf) {
   const double frac = (x - lt.x_min) * lt.inv_fac;
   if (frac <= 0) {
@@ -619,12 +600,6 @@ __global__ void __launch_bounds__(256)
 }
 
 // ------------------------------------------------------------ update
-struct DevReaction {
-  int rate_type, table_col, n_in, n_out;
-  double rate_factor, c[4];
-  int ix_in[4], ix_out[4], mult_out[4];
-};
-
 struct UpdArgs {
   int ns, nr, n_prev, last_step, e_index;  // e_index: species slot of the flux species
   int der_q;  // s_deriv == s_prev[der_q] (the derivative state is read once), or -1
@@ -635,8 +610,8 @@ struct UpdArgs {
   const double *E;
   const double *F;
   const DevReaction *reac;
-  DevLT chem;
-  DevLT td;        // transport table (mean-energy column for Te)
+  DevLTrm chem;
+  DevLTrm td;        // transport table (mean-energy column for Te)
   int te_col;      // td_energy_eV column (1-based), 0 if absent
   double Tg;       // gas temperature
   double inv_N;
@@ -713,62 +688,10 @@ template <bool SF, bool RS>
 using UpdArgsOf = std::conditional_t<RS, std::conditional_t<SF, UpdArgsSfRs, UpdArgsRs>,
                                      std::conditional_t<SF, UpdArgsSf, UpdArgs>>;
 
-// the wave's sum in a fixed order (the xor butterfly: every lane ends with
-// the same bits); every lane of the wave must be active
-__device__ __forceinline__ double wave_sum(double v) {
-  for (int o = 32; o > 0; o >>= 1) v = v + __shfl_xor(v, o, 64);
-  return v;
-}
-// the wave partials of a k_update<..., RS> workgroup: [nr + 1][4 waves]
-__device__ __forceinline__ double *rate_sum_lds() {
-  __shared__ double w[(AFH_MAX_REACTIONS + 1) * 4];
-  return w;
-}
-
-// adds the rows of part in a fixed order: one workgroup per column (reaction,
-// J.E), lane q the rows q, q + 256, ... in turn, then the lanes' sums by
-// halving through LDS
 __global__ void __launch_bounds__(256)
     k_rate_fold(const double *__restrict__ part, int n_rows, int n_col,
                 double *__restrict__ out) {
-  const int c = blockIdx.x;
-  double s = 0.0;
-  for (int r = threadIdx.x; r < n_rows; r += 256) s = s + part[(size_t)r * n_col + c];
-  __shared__ double w[256];
-  w[threadIdx.x] = s;
-  __syncthreads();
-  for (int h = 128; h > 0; h >>= 1) {
-    if ((int)threadIdx.x < h) w[threadIdx.x] = w[threadIdx.x] + w[threadIdx.x + h];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[c] = w[0];
-}
-
-// NORM2 of (a, b, c) as the Fortran runtime of the reference build evaluates
-// it (element by element: the largest magnitude m so far, s = the sum of
-// (x / m)^2 over the others, rescaled when m grows; m sqrt(1 + s)) -- not
-// sqrt(a a + b b + c c), which differs in the last bit for about a third of
-// all inputs. afh.electrode.norm2 is the same evaluation on the host.
-__device__ __forceinline__ void norm2_acc(double x, double &m, double &s) {
-  const double a = fabs(x);
-  if (m == 0.0) {
-    m = a;
-  } else if (a > m) {
-    const double t = m / a, tsq = t * t;
-    s = s * tsq;
-    s = s + tsq;
-    m = a;
-  } else {
-    const double t = a / m;
-    s = s + t * t;
-  }
-}
-__device__ __forceinline__ double norm2_3(double a, double b, double c) {
-  double m = 0.0, s = 0.0;
-  norm2_acc(a, m, s);
-  norm2_acc(b, m, s);
-  norm2_acc(c, m, s);
-  return m * sqrt(1 + s);
+  rate_fold(part, n_rows, n_col, out);
 }
 
 // Register-resident species arrays indexed by runtime reaction data (the
@@ -842,9 +765,17 @@ __device__ __forceinline__ double rate_slow(const UpdArgs &A, const DevReaction 
 // reaction reads its column from the two rows of a row-major copy of the
 // table (one or two cache lines per cell instead of two per reaction); same
 // expression as LT_get_col_at_loc, bitwise.
-__device__ __forceinline__ double lt_at_rm(const DevLT &lt, int col, int low, double lf) {
+__device__ __forceinline__ double lt_at_rm(const DevLTrm &lt, int col, int low, double lf) {
   const double *r = lt.rm + (size_t)(low - 1) * lt.n_cols + (col - 1);
   return lf * r[0] + (1 - lf) * r[lt.n_cols];
+}
+
+// the chemistry table's column at the cell's field: from the location found
+// once per cell (low > 0), else by lt_col
+__device__ __forceinline__ auto chem_tab(const UpdArgs &A, double field, int low, double lf) {
+  return [&A, field, low, lf](int col) {
+    return low > 0 ? lt_at_rm(A.chem, col, low, lf) : lt_col(A.chem, col, field);
+  };
 }
 
 template <bool SLOW>
@@ -853,20 +784,14 @@ __device__ __forceinline__ double rate_of(const UpdArgs &A, const DevReaction &R
                                           double lf = 0.0) {
   const double c0 = R.rate_factor;
   const double *c = R.c;
+  const auto tab = chem_tab(A, field, low, lf);
   switch (R.rate_type) {
   case AFH_RATE_TABULATED_FIELD:
-    return c0 * (low > 0 ? lt_at_rm(A.chem, R.table_col, low, lf)
-                         : lt_col(A.chem, R.table_col, field));
-  case AFH_RATE_CONSTANT: return c0 * c[0];
-  case AFH_RATE_LINEAR: return c0 * c[0] * (field - c[1]);
-  case AFH_RATE_EXP_V1: {
-    const double z = c[1] / (c[2] + field);
-    return c0 * c[0] * exp(-(z * z));
-  }
-  case AFH_RATE_EXP_V2: {
-    const double z = field / c[1];
-    return c0 * c[0] * exp(-(z * z));
-  }
+    return field_form<AFH_RATE_TABULATED_FIELD>(c0, c, R.table_col, field, tab);
+  case AFH_RATE_CONSTANT: return field_form<AFH_RATE_CONSTANT>(c0, c, 0, field, tab);
+  case AFH_RATE_LINEAR: return field_form<AFH_RATE_LINEAR>(c0, c, 0, field, tab);
+  case AFH_RATE_EXP_V1: return field_form<AFH_RATE_EXP_V1>(c0, c, 0, field, tab);
+  case AFH_RATE_EXP_V2: return field_form<AFH_RATE_EXP_V2>(c0, c, 0, field, tab);
   default: return SLOW ? rate_slow(A, R, field, Te) : 0.0;
   }
 }
@@ -881,21 +806,8 @@ __device__ __forceinline__ double rate_of(const UpdArgs &A, const DevReaction &R
 template <int T, bool SLOW>
 __device__ __forceinline__ double rate_t(const UpdArgs &A, const DevReaction &R, double field,
                                          double &Te, int low, double lf) {
-  const double c0 = R.rate_factor;
-  const double *c = R.c;
-  if constexpr (T == AFH_RATE_TABULATED_FIELD) {
-    return c0 * (low > 0 ? lt_at_rm(A.chem, R.table_col, low, lf)
-                         : lt_col(A.chem, R.table_col, field));
-  } else if constexpr (T == AFH_RATE_CONSTANT) {
-    return c0 * c[0];
-  } else if constexpr (T == AFH_RATE_LINEAR) {
-    return c0 * c[0] * (field - c[1]);
-  } else if constexpr (T == AFH_RATE_EXP_V1) {
-    const double z = c[1] / (c[2] + field);
-    return c0 * c[0] * exp(-(z * z));
-  } else if constexpr (T == AFH_RATE_EXP_V2) {
-    const double z = field / c[1];
-    return c0 * c[0] * exp(-(z * z));
+  if constexpr (T <= AFH_RATE_EXP_V2) {
+    return field_rate<T>(R, field, chem_tab(A, field, low, lf));
   } else {
     static_assert(SLOW, "temperature-dependent rate form in a fast update");
     return rate_slow(A, R, field, Te);
@@ -1013,7 +925,7 @@ __device__ __forceinline__ double upwind_t(int lim, double Lm2, double Lm1,
 
 // LT_get_loc + LT_get_col for mobility and diffusion from the interleaved LDS
 // table T[2 r] = mu N (row r+1), T[2 r + 1] = D N (lt_mu_dc order)
-__device__ __forceinline__ void lds_mu_dc(const double *T, const DevLT &lt,
+__device__ __forceinline__ void lds_mu_dc(const double *T, const DevLTrm &lt,
                                           double x, double &mu, double &dc) {
   int low;
   double lf;
@@ -2140,7 +2052,7 @@ __global__ void __launch_bounds__(NTT, AFH_FE_MINW)
 // reference's order. Same expressions as oracle/c/afo.c refine_cell.
 struct RefineArgs {
   afh_refine_desc d;
-  DevLT td;
+  DevLTrm td;
   double N;
   const double *ne, *E;
   const double *Ng;     // gas density per cell (variable N), or null
@@ -2310,7 +2222,7 @@ struct afh_fluid {
   double *d_td = nullptr, *d_chem = nullptr, *d_chem_rm = nullptr;
   DevReaction *d_reac = nullptr;
   int e_index = -1;
-  DevLT td, chem;
+  DevLTrm td, chem;
   // k_flux_lds: transport table interleaved per row (mu N, D N); unset when
   // the table does not fit LDS: k_flux_staged
   double *d_tdi = nullptr;
@@ -2341,12 +2253,7 @@ struct afh_fluid {
   int sf_mode = 0, sf_iv = 0;
   double sf_min_e = 0.0;
   uint8_t *d_sf_ion = nullptr;
-  // afh_fluid_set_rate_sums: on, the workgroups' partial rows (rs_cap rows of
-  // n_reactions + 1 doubles; regrown when the tree has more leaves), the
-  // folded result on the device and whether a last step has filled it
-  bool rs_on = false, rs_valid = false;
-  double *d_rs_part = nullptr, *d_rs_out = nullptr;
-  size_t rs_cap = 0;
+  RateSums rs;  // afh_fluid_set_rate_sums
   // mobile ions: second ghost layers of each ion [ion][box][6][nc][nc] and
   // the electrons' mu u per face (k_flux_staged -> k_flux_ion)
   double *d_gc2_ion = nullptr, *d_sig = nullptr;
@@ -2383,6 +2290,8 @@ int32_t afh_fluid_create(afh_tree *t, const afh_fluid_desc *d, afh_fluid **out) 
   afh_fluid *f = new afh_fluid();
   f->t = t;
   f->d = *d;
+  // (destroyed on every error return below)
+  std::unique_ptr<afh_fluid, int32_t (*)(afh_fluid *)> hold(f, afh_fluid_destroy);
   for (int s = 0; s < d->n_species; s++) {
     if (d->species_iv[s] < 1 || d->species_iv[s] > t->nvc)
       return set_error(AFH_ERR_ARG, "bad species index");
@@ -2443,10 +2352,8 @@ int32_t afh_fluid_create(afh_tree *t, const afh_fluid_desc *d, afh_fluid **out) 
     AFH_HIP(hipMemcpy(f->d_tdi, ti.data(), ti.size() * sizeof(double),
                       hipMemcpyHostToDevice));
   }
-  std::vector<DevReaction> R(std::max(1, d->n_reactions));
   for (int r = 0; r < d->n_reactions; r++) {
     const afh_reaction &a = d->reactions[r];
-    DevReaction &b = R[r];
     if (a.rate_type < AFH_RATE_TABULATED_FIELD || a.rate_type > AFH_RATE_K15 ||
         a.rate_type == 7)
       return set_error(AFH_ERR_UNSUPPORTED, "reaction rate type %d", a.rate_type);
@@ -2457,20 +2364,6 @@ int32_t afh_fluid_create(afh_tree *t, const afh_fluid_desc *d, afh_fluid **out) 
                        a.rate_type);
     if (a.n_in < 0 || a.n_in > 4 || a.n_out < 0 || a.n_out > 4)
       return set_error(AFH_ERR_ARG, "reaction species count");
-    b.rate_type = a.rate_type;
-    b.table_col = a.table_col;
-    b.n_in = a.n_in;
-    b.n_out = a.n_out;
-    b.rate_factor = a.rate_factor;
-    // species indices: 1..ng gas, then the plasma species (the reference's
-    // order); the kernels keep the plasma species first, the gas after them
-    auto remap = [&](int ix) { return ix <= ng ? d->n_species + ix : ix - ng; };
-    for (int q = 0; q < 4; q++) {
-      b.c[q] = a.c[q];
-      b.ix_in[q] = q < a.n_in ? remap(a.ix_in[q]) : a.ix_in[q];
-      b.ix_out[q] = q < a.n_out ? remap(a.ix_out[q]) : a.ix_out[q];
-      b.mult_out[q] = a.mult_out[q];
-    }
     for (int q = 0; q < a.n_in; q++)
       if (a.ix_in[q] < 1 || a.ix_in[q] > ng + d->n_species)
         return set_error(AFH_ERR_ARG, "reaction species index");
@@ -2490,13 +2383,15 @@ int32_t afh_fluid_create(afh_tree *t, const afh_fluid_desc *d, afh_fluid **out) 
     if (env && atoi(env) == 2 && !f->net)
       return set_error(AFH_ERR_UNSUPPORTED, "no compiled reaction network matches");
   }
-  AFH_HIP(hipMalloc(&f->d_reac, sizeof(DevReaction) * R.size()));
-  AFH_HIP(hipMemcpy(f->d_reac, R.data(), sizeof(DevReaction) * R.size(),
-                    hipMemcpyHostToDevice));
-  f->td = DevLT{d->td.n_points, d->td.n_cols, d->td.x_min, d->td.inv_fac, f->d_td};
-  f->chem = DevLT{d->chem.n_points, d->chem.n_cols, d->chem.x_min,
-                  d->chem.inv_fac, f->d_chem, f->d_chem_rm};
-  *out = f;
+  // species indices: 1..ng gas, then the plasma species (the reference's
+  // order); the kernels keep the plasma species first, the gas after them
+  if (int32_t e = upload_reactions(
+          d, [&](int ix) { return ix <= ng ? d->n_species + ix : ix - ng; }, &f->d_reac))
+    return e;
+  f->td = DevLTrm{{d->td.n_points, d->td.n_cols, d->td.x_min, d->td.inv_fac, f->d_td}};
+  f->chem = DevLTrm{{d->chem.n_points, d->chem.n_cols, d->chem.x_min, d->chem.inv_fac,
+                     f->d_chem}, f->d_chem_rm};
+  *out = hold.release();
   return AFH_OK;
 }
 
@@ -2513,8 +2408,7 @@ int32_t afh_fluid_destroy(afh_fluid *f) {
   hipFree(f->d_sig);
   hipFree(f->d_mstat);
   hipFree(f->d_sf_ion);
-  hipFree(f->d_rs_part);
-  hipFree(f->d_rs_out);
+  f->rs.release();
   delete f;
   return AFH_OK;
 }
@@ -2569,60 +2463,17 @@ int32_t afh_fluid_set_update_mask(afh_fluid *f, int32_t i_lsf) {
 int32_t afh_fluid_set_source_factor(afh_fluid *f, int32_t mode, const uint8_t *ionization,
                                     double min_electrons_per_cell, int32_t i_srcfac) {
   if (!f) return set_error(AFH_ERR_ARG, "afh_fluid_set_source_factor: null");
-  afh_tree *t = f->t;
-  AFH_LIVE(t, "afh_fluid_set_source_factor");
-  if (mode != AFH_SRCFAC_NONE && mode != AFH_SRCFAC_FLUX)
-    return set_error(AFH_ERR_ARG, "afh_fluid_set_source_factor: unknown mode %d", mode);
-  if (mode == AFH_SRCFAC_FLUX && !ionization)
-    return set_error(AFH_ERR_ARG, "afh_fluid_set_source_factor: no ionization flags");
-  if (i_srcfac < 0 || i_srcfac > t->nvc)
-    return set_error(AFH_ERR_ARG, "afh_fluid_set_source_factor: bad i_srcfac %d", i_srcfac);
-  // (the other states of the species: upd_args, with the states of the step)
-  bool used = i_srcfac > 0 && (i_srcfac == f->d.i_efld || i_srcfac == f->d.i_photo ||
-                               i_srcfac == f->d.i_gas_dens || i_srcfac == f->mask_iv ||
-                               i_srcfac == f->rhs_iv);
-  for (int s = 0; s < f->d.n_species && i_srcfac > 0; s++)
-    used = used || i_srcfac == f->d.species_iv[s];
-  if (used)
-    return set_error(AFH_ERR_ARG,
-                     "afh_fluid_set_source_factor: i_srcfac %d is a variable the step uses",
-                     i_srcfac);
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  AFH_HIP(hipStreamIsCapturing(t->stream, &cs));
-  if (cs != hipStreamCaptureStatusNone)
-    return set_error(AFH_ERR_STATE, "afh_fluid_set_source_factor during a graph capture");
-  if (mode == AFH_SRCFAC_FLUX && f->d.n_reactions > 0) {
-    // (a queued update may still read the previous flags)
-    AFH_HIP(hipStreamSynchronize(t->stream));
-    if (!f->d_sf_ion) AFH_HIP(hipMalloc(&f->d_sf_ion, AFH_MAX_REACTIONS));
-    uint8_t flags[AFH_MAX_REACTIONS];
-    for (int r = 0; r < f->d.n_reactions; r++) flags[r] = ionization[r] ? 1 : 0;
-    AFH_HIP(hipMemcpy(f->d_sf_ion, flags, f->d.n_reactions, hipMemcpyHostToDevice));
-  }
-  f->sf_mode = mode;
-  f->sf_min_e = min_electrons_per_cell;
-  f->sf_iv = i_srcfac;
-  return AFH_OK;
+  AFH_LIVE(f->t, "afh_fluid_set_source_factor");
+  return set_source_factor(f, mode, ionization, min_electrons_per_cell, i_srcfac,
+                           i_srcfac == f->rhs_iv);
 }
 
 // the partial rows of a last step with the sums on: one per update workgroup
 // of every leaf
-static int32_t rate_sums_reserve(afh_fluid *f) {
-  afh_tree *t = f->t;
+static size_t rate_sum_rows(const afh_fluid *f) {
+  const afh_tree *t = f->t;
   const int nc = t->nc, n3 = nc * nc * nc;
-  const size_t rows = (size_t)t->leaves.off[t->nlvl] * ((n3 / AFH_UPD_KC + 255) / 256);
-  const size_t ncol = (size_t)f->d.n_reactions + 1;
-  if (!f->d_rs_out) AFH_HIP(hipMalloc(&f->d_rs_out, ncol * sizeof(double)));
-  if (rows > f->rs_cap) {
-    // (a queued fold may still read the old rows)
-    AFH_HIP(hipStreamSynchronize(t->stream));
-    hipFree(f->d_rs_part);
-    f->d_rs_part = nullptr;
-    f->rs_cap = 0;
-    AFH_HIP(hipMalloc(&f->d_rs_part, rows * ncol * sizeof(double)));
-    f->rs_cap = rows;
-  }
-  return AFH_OK;
+  return (size_t)t->leaves.off[t->nlvl] * ((n3 / AFH_UPD_KC + 255) / 256);
 }
 
 int32_t afh_fluid_set_rate_sums(afh_fluid *f, int32_t on) {
@@ -2633,35 +2484,14 @@ int32_t afh_fluid_set_rate_sums(afh_fluid *f, int32_t on) {
     return set_error(AFH_ERR_UNSUPPORTED,
                      "afh_fluid_set_rate_sums: the sums over the ranks of a sharded tree "
                      "are not built");
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  AFH_HIP(hipStreamIsCapturing(t->stream, &cs));
-  if (cs != hipStreamCaptureStatusNone)
-    return set_error(AFH_ERR_STATE, "afh_fluid_set_rate_sums during a graph capture");
-  if (on && !f->rs_on) {
-    if (int32_t e = rate_sums_reserve(f)) return e;
-    f->rs_valid = false;
-  }
-  f->rs_on = on != 0;
-  return AFH_OK;
+  return f->rs.set(on != 0, rate_sum_rows(f), (size_t)f->d.n_reactions + 1, t->stream);
 }
 
 int32_t afh_fluid_fetch_rate_sums(afh_fluid *f, double *rates, double *jdote) {
   if (!f || !jdote || (!rates && f->d.n_reactions > 0))
     return set_error(AFH_ERR_ARG, "afh_fluid_fetch_rate_sums: null");
-  afh_tree *t = f->t;
-  AFH_LIVE(t, "afh_fluid_fetch_rate_sums");
-  if (!f->rs_on) return set_error(AFH_ERR_STATE, "afh_fluid_fetch_rate_sums: the sums are off");
-  if (!f->rs_valid)
-    return set_error(AFH_ERR_STATE,
-                     "afh_fluid_fetch_rate_sums: no last step since the sums were switched on");
-  const int nr = f->d.n_reactions;
-  double h[AFH_MAX_REACTIONS + 1];
-  AFH_HIP(hipMemcpyAsync(h, f->d_rs_out, (nr + 1) * sizeof(double), hipMemcpyDeviceToHost,
-                         t->stream));
-  AFH_HIP(hipStreamSynchronize(t->stream));
-  for (int r = 0; r < nr; r++) rates[r] = h[r];
-  *jdote = h[nr];
-  return AFH_OK;
+  AFH_LIVE(f->t, "afh_fluid_fetch_rate_sums");
+  return f->rs.fetch(f->d.n_reactions, f->t->stream, rates, jdote);
 }
 
 int32_t afh_fluid_set_rhs_output(afh_fluid *f, int32_t i_rhs, int32_t ghosts) {
@@ -3178,11 +3008,11 @@ static int32_t update_dev(afh_fluid *f, double dt, int32_t s_deriv, int32_t n_pr
   const bool all_lvls = t->all_lvl_launch && t->leaves.off[t->nlvl] <= 65535;
   if (all_lvls) A.meta = t->d_boxes;
   // the rate sums (afh_fluid_set_rate_sums): last steps only
-  const bool rs_on = f->rs_on && last_step;
+  const bool rs_on = f->rs.on && last_step;
   if (rs_on) {
     if (t->hook || t->dev_reduce)
       return set_error(AFH_ERR_UNSUPPORTED, "the rate sums on a sharded tree are not built");
-    if ((e = rate_sums_reserve(f))) return e;
+    if ((e = f->rs.reserve(rate_sum_rows(f), (size_t)f->d.n_reactions + 1, t->stream))) return e;
   }
   const int upd_gx = (n3 / AFH_UPD_KC + 255) / 256;
   for (int l = 1; l <= t->nlvl; l++) {
@@ -3191,7 +3021,7 @@ static int32_t update_dev(afh_fluid *f, double dt, int32_t s_deriv, int32_t n_pr
     for (int q = 0; q < 3; q++) A.dt_dr[q] = dt / t->lvl_dr[3 * (l - 1) + q];
     RateSumArgs RS;
     if (rs_on) {
-      RS.part = f->d_rs_part;
+      RS.part = f->rs.part;
       RS.row0 = t->leaves.off[l - 1] * upd_gx;
       RS.Ef = t->fcv(f->d.f_field);
       RS.phi = f->phi_iv > 0 ? t->ccv(f->phi_iv) : nullptr;
@@ -3226,10 +3056,10 @@ static int32_t update_dev(afh_fluid *f, double dt, int32_t s_deriv, int32_t n_pr
     AFH_LAUNCH_CHECK("k_update");
   }
   if (rs_on) {
-    hipLaunchKernelGGL(k_rate_fold, dim3(A.nr + 1), dim3(256), 0, t->stream, f->d_rs_part,
-                       t->leaves.off[t->nlvl] * upd_gx, A.nr + 1, f->d_rs_out);
+    hipLaunchKernelGGL(k_rate_fold, dim3(A.nr + 1), dim3(256), 0, t->stream, f->rs.part,
+                       t->leaves.off[t->nlvl] * upd_gx, A.nr + 1, f->rs.out);
     AFH_LAUNCH_CHECK("k_rate_fold");
-    f->rs_valid = true;
+    f->rs.valid = true;
   }
   if (A.rhs) {
     // the ghost shell of rhs from the ghost cells of the new state (the
@@ -3404,7 +3234,7 @@ static int32_t fe_dev(afh_fluid *f, double dt, int32_t s_deriv, int32_t n_prev,
                      f->d.i_photo <= 0 && n_prev <= 2 && !alias &&
                      f->d.limiter == AFH_LIM_KOREN && f->d.n_ions == 0 && !f->mask_iv &&
                      f->sf_mode == AFH_SRCFAC_NONE &&  // (k_fe_lds has no source factor
-                     !(f->rs_on && last_step);          // and forms no rate sums)
+                     !(f->rs.on && last_step);          // and forms no rate sums)
   if (!fused) {
     // flux and update back to back on the stream (the flux maxima are not
     // needed before the update); secondary emission from ions at the walls
@@ -3565,7 +3395,7 @@ namespace afh {
 __global__ void k_photoi_src(double *__restrict__ rhs, const double *__restrict__ E,
                              const double *__restrict__ ne,
                              const double *__restrict__ Ng, double N,
-                             DevLT td, int alpha_col, double coeff,
+                             DevLTrm td, int alpha_col, double coeff,
                              const int32_t *__restrict__ ids, int nc, size_t bsz) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= nc * nc * nc) return;

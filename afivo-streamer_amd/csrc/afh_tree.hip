@@ -22,58 +22,11 @@
 
 namespace afh {
 
-static thread_local char g_err[512];
-
-int32_t set_error(int32_t code, const char *fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof g_err, fmt, ap);
-  va_end(ap);
-  return code;
-}
-
-int32_t check_hip(hipError_t e, const char *what) {
-  return set_error(AFH_ERR_DEVICE, "%s: %s", what, hipGetErrorString(e));
-}
-
 int32_t pool_alloc(void **p, size_t bytes, const char *what) {
   (void)what;
   *p = nullptr;
   AFH_HIP(hipMalloc(p, bytes));
   return AFH_OK;
-}
-
-static hipEvent_t next_event(afh_tree *t) {
-  if (t->ev_used == t->ev_pool.size()) {
-    hipEvent_t e;
-    hipEventCreate(&e);
-    t->ev_pool.push_back(e);
-  }
-  return t->ev_pool[t->ev_used++];
-}
-
-void prof_begin(afh_tree *t, int kc) {
-  if (t->prof_class != kc) return;
-  hipEventRecord(next_event(t), t->stream);
-}
-
-bool prof_ext(afh_tree *t, int kc, hipEvent_t &e0, hipEvent_t &e1) {
-  if (t->prof_class != kc) return false;
-  e0 = next_event(t);
-  e1 = next_event(t);
-  return true;
-}
-
-void prof_count(afh_tree *t, double bytes) {
-  t->prof_bytes += bytes;
-  t->prof_launches++;
-}
-
-void prof_end(afh_tree *t, int kc, double bytes) {
-  if (t->prof_class != kc) return;
-  hipEventRecord(next_event(t), t->stream);
-  t->prof_bytes += bytes;
-  t->prof_launches++;
 }
 
 // ------------------------------------------------------------ faces
@@ -722,23 +675,6 @@ __global__ void k_box_reduce(const double *__restrict__ v,
   }
 }
 
-int32_t upload_list(afh_tree *t, LevelList &L,
-                    const std::vector<std::vector<int32_t>> &lists) {
-  if (L.d) hipFree(L.d), L.d = nullptr;
-  L.off.assign(lists.size() + 1, 0);
-  std::vector<int32_t> flat;
-  for (size_t l = 0; l < lists.size(); l++) {
-    flat.insert(flat.end(), lists[l].begin(), lists[l].end());
-    L.off[l + 1] = (int32_t)flat.size();
-  }
-  AFH_HIP(hipMalloc(&L.d, sizeof(int32_t) * (flat.size() + 1)));
-  if (!flat.empty())
-    AFH_HIP(hipMemcpy(L.d, flat.data(), sizeof(int32_t) * flat.size(),
-                      hipMemcpyHostToDevice));
-  return AFH_OK;
-}
-
-
 // ------------------------------------------------------------ regrid
 // af_prolong_limit / af_prolong_linear (m_af_prolong.f90:311-420, 531-679),
 // add = .false.: one thread per parent cell of the child's octant writes
@@ -816,7 +752,7 @@ using namespace afh;
 
 extern "C" {
 
-const char *afh_last_error(void) { return afh::g_err; }
+const char *afh_last_error(void) { return afhc::err_text(); }
 
 
 static int32_t tree_create_impl(const afh_tree_desc *d, int32_t device,
@@ -936,11 +872,11 @@ static int32_t tree_create_impl(const afh_tree_desc *d, int32_t device,
     }
   }
   int32_t e;
-  if ((e = upload_list(t, t->ids, t->h_ids)) ||
-      (e = upload_list(t, t->leaves, t->h_leaves)) ||
-      (e = upload_list(t, t->parents, t->h_parents)) ||
-      (e = upload_list(t, t->refb, refb)) || (e = upload_list(t, t->cflux, cfl)) ||
-      (e = upload_list(t, t->xrb, xrb)))
+  if ((e = upload_list(t->ids, t->h_ids)) ||
+      (e = upload_list(t->leaves, t->h_leaves)) ||
+      (e = upload_list(t->parents, t->h_parents)) ||
+      (e = upload_list(t->refb, refb)) || (e = upload_list(t->cflux, cfl)) ||
+      (e = upload_list(t->xrb, xrb)))
     return e;
   AFH_HIP(hipMalloc(&t->d_boxes, sizeof(afh_box_meta) * t->nb));
   AFH_HIP(hipMemcpy(t->d_boxes, t->boxes.data(), sizeof(afh_box_meta) * t->nb,
@@ -987,32 +923,14 @@ int32_t afh_tree_create(const afh_tree_desc *d, int32_t device,
 
 int32_t afh_profile_enable(afh_tree *t, int32_t kclass) {
   AFH_LIVE(t, "afh_profile_enable");
-  AFH_HIP(hipStreamSynchronize(t->stream));
-  t->prof_class = kclass;
-  t->ev_used = 0;
-  t->prof_bytes = 0;
-  t->prof_launches = 0;
-  return AFH_OK;
+  return profile_enable(t, kclass);
 }
 
 int32_t afh_profile_read(afh_tree *t, double *total_ms, int64_t *launches,
                          double *bytes) {
   if (!t || !total_ms || !launches || !bytes)
     return set_error(AFH_ERR_ARG, "null argument");
-  AFH_HIP(hipStreamSynchronize(t->stream));
-  double ms = 0;
-  for (size_t q = 0; q + 1 < t->ev_used; q += 2) {
-    float e = 0;
-    AFH_HIP(hipEventElapsedTime(&e, t->ev_pool[q], t->ev_pool[q + 1]));
-    ms += e;
-  }
-  *total_ms = ms;
-  *launches = t->prof_launches;
-  *bytes = t->prof_bytes;
-  t->ev_used = 0;
-  t->prof_bytes = 0;
-  t->prof_launches = 0;
-  return AFH_OK;
+  return profile_read(t, total_ms, launches, bytes);
 }
 
 // The boxes of level lvl of a topology whose x faces a fill without x faces
@@ -1034,7 +952,7 @@ int32_t afh_xface_rb_boxes(const afh_tree_desc *d, int32_t lvl, int32_t *out, in
 int32_t afh_tree_destroy(afh_tree *t) {
   if (!t) return AFH_OK;
   hipStreamSynchronize(t->stream);
-  for (hipEvent_t e : t->ev_pool) hipEventDestroy(e);
+  for (hipEvent_t e : t->prof.ev_pool) hipEventDestroy(e);
   for (LevelList *L : {&t->ids, &t->leaves, &t->parents, &t->refb, &t->cflux, &t->xrb})
     hipFree(L->d);
   for (auto &p : t->plans) {
@@ -1368,16 +1286,10 @@ int32_t afh_tree_sum_cc(afh_tree *t, int32_t iv, int32_t power, double *out) {
   }
   if ((e = box_reduce(t, iv, 0, power, res))) return e;
   // my_sum = my_sum + fac * tmp, fac = product(af_lvl_dr(tree, lvl))
-  double sum = 0.0;
-  size_t q = 0;
-  for (int l = 1; l <= t->nlvl; l++) {
-    const double *dr = &t->lvl_dr[3 * (l - 1)];
-    const double fac = dr[0] * dr[1] * dr[2];
-    for (int b = 0; b < t->leaves.n(l); b++, q++)
-      if (t->sum_skip.empty() || !t->sum_skip[t->h_leaves[l - 1][b] - 1])
-        sum = sum + fac * res[2 * q];
-  }
-  *out = sum;
+  std::vector<double> fac(t->nlvl);
+  for (int l = 0; l < t->nlvl; l++)
+    fac[l] = t->lvl_dr[3 * l] * t->lvl_dr[3 * l + 1] * t->lvl_dr[3 * l + 2];
+  *out = fold_leaf_sums(res, fac, t->h_leaves, &t->sum_skip);
   return call_hook(t, AFH_HOOK_SUM, 0, iv, out, 1);
 }
 
@@ -1391,23 +1303,9 @@ int32_t afh_tree_reduce_loc(afh_tree *t, int32_t iv, int32_t op, double *out,
   std::vector<double> res;
   int32_t e;
   if ((e = box_reduce(t, iv, op, 1, res))) return e;
-  // af_reduction_loc: init -huge/10 (max) or huge/10 (min); a box replaces
-  // the running value when reduction(tmp, val) differs from val
   const bool is_min = op == AFH_RED_MIN;
-  double val = (is_min ? 1 : -1) * (DBL_MAX / 10);
-  int32_t lid = -1, lix = -1;
-  size_t q = 0;
-  for (int l = 1; l <= t->nlvl; l++)
-    for (int b = 0; b < t->leaves.n(l); b++, q++) {
-      const double tmp = res[2 * q];
-      const double nv = is_min ? std::min(tmp, val) : std::max(tmp, val);
-      if (std::fabs(nv - val) > 0) {
-        val = tmp;
-        lid = t->h_leaves[l - 1][b];
-        lix = (int32_t)res[2 * q + 1];
-      }
-    }
-  *out = val;
+  int32_t lid, lix;
+  *out = fold_leaf_best(res, t->h_leaves, is_min, lid, lix);
   if (loc) {
     loc[0] = lid;
     const int nc = t->nc;
@@ -1418,88 +1316,30 @@ int32_t afh_tree_reduce_loc(afh_tree *t, int32_t iv, int32_t op, double *out,
   return call_hook(t, is_min ? AFH_HOOK_MIN : AFH_HOOK_MAX, 0, iv, out, 1);
 }
 
-// The reductions of afivo_hip_analysis.h (kernels and launchers:
-// afh_analysis_dev.h). The launchers' view of the tree, with the per-leaf
-// scratch and the result buffer (4 + n_list doubles) grown to fit.
-static int32_t an_ctx(afh_tree *t, size_t n_list, const char *what, afh_an::Ctx &c) {
-  if (t->hook || t->dev_reduce)
-    return set_error(AFH_ERR_UNSUPPORTED, "%s: the fold over the ranks of a sharded tree is "
-                     "not built", what);
-  const int nl = t->leaves.off[t->nlvl];
-  if (nl > t->boxred_cap) {
-    AFH_HIP(hipStreamSynchronize(t->stream));
-    hipFree(t->d_boxred);
-    t->d_boxred = nullptr, t->boxred_cap = 0;
-    AFH_HIP(hipMalloc(&t->d_boxred, sizeof(double) * 2 * nl));
-    t->boxred_cap = nl;
-  }
-  if (4 + n_list > t->an_cap) {
-    AFH_HIP(hipStreamSynchronize(t->stream));
-    hipFree(t->d_an);
-    t->d_an = nullptr, t->an_cap = 0;
-    AFH_HIP(hipMalloc(&t->d_an, sizeof(double) * (4 + n_list)));
-    t->an_cap = 4 + n_list;
-  }
-  c.stream = t->stream;
-  c.nd = 3, c.nc = t->nc, c.nl = nl;
-  c.leaves = t->leaves.d;
-  c.meta = t->d_boxes;
-  c.part = t->d_boxred, c.res = t->d_an;
-  return AFH_OK;
-}
-
+// The reductions of afivo_hip_analysis.h (kernels, launchers and the bodies
+// of the entry points: afh_analysis_dev.h), which refuse a sharded tree.
 int32_t afh_tree_reduce_fc(afh_tree *t, int32_t ivf, int32_t dim, int32_t op, double *out,
                            int32_t *loc) {
   AFH_LIVE(t, "afh_tree_reduce_fc");
-  if (ivf < 1 || ivf > t->nvf || dim < 1 || dim > 3 || !out ||
-      (op != AFH_RED_MAX && op != AFH_RED_MIN))
-    return set_error(AFH_ERR_ARG, "afh_tree_reduce_fc: bad argument");
-  afh_an::Ctx c;
-  if (int32_t e = an_ctx(t, 0, "afh_tree_reduce_fc", c)) return e;
-  const bool is_min = op == AFH_RED_MIN;
-  afh_an::Region none = {};
-  AFH_HIP(afh_an::best_loc(c, t->fcv(ivf), afh_an::geo_fc(3, t->nc, t->fsz, dim - 1), is_min,
-                           none, (is_min ? 1 : -1) * (DBL_MAX / 10), out, loc));
-  return AFH_OK;
+  return afh_an::reduce_fc<3>(t, ivf, dim, op, out, loc);
 }
 
 int32_t afh_tree_zminmax_threshold(afh_tree *t, int32_t iv, double threshold,
                                    const double *limits, double *out) {
   AFH_LIVE(t, "afh_tree_zminmax_threshold");
-  if (iv < 1 || iv > t->nvc || !limits || !out)
-    return set_error(AFH_ERR_ARG, "afh_tree_zminmax_threshold: bad argument");
-  afh_an::Ctx c;
-  if (int32_t e = an_ctx(t, 0, "afh_tree_zminmax_threshold", c)) return e;
-  AFH_HIP(afh_an::zminmax(c, t->ccv(iv), afh_an::geo_cc(3, t->nc, t->bsz), threshold, limits,
-                          out));
-  return AFH_OK;
+  return afh_an::zminmax_threshold<3>(t, iv, threshold, limits, out);
 }
 
 int32_t afh_tree_max_region(afh_tree *t, int32_t iv, const double *r0, const double *r1,
                             double *out, int32_t *loc) {
   AFH_LIVE(t, "afh_tree_max_region");
-  if (iv < 1 || iv > t->nvc || !r0 || !r1 || !out)
-    return set_error(AFH_ERR_ARG, "afh_tree_max_region: bad argument");
-  afh_an::Ctx c;
-  if (int32_t e = an_ctx(t, 0, "afh_tree_max_region", c)) return e;
-  afh_an::Region R = {};
-  R.on = 1;
-  for (int d = 0; d < 3; d++) R.r0[d] = r0[d], R.r1[d] = r1[d];
-  AFH_HIP(afh_an::best_loc(c, t->ccv(iv), afh_an::geo_cc(3, t->nc, t->bsz), false, R, -1e100,
-                           out, loc));
-  return AFH_OK;
+  return afh_an::max_region<3>(t, iv, r0, r1, out, loc);
 }
 
 int32_t afh_tree_local_maxima(afh_tree *t, int32_t iv, double threshold, int32_t n_max,
                               double *coord_val, int32_t *n_found) {
   AFH_LIVE(t, "afh_tree_local_maxima");
-  if (iv < 1 || iv > t->nvc || n_max < 0 || (n_max > 0 && !coord_val) || !n_found)
-    return set_error(AFH_ERR_ARG, "afh_tree_local_maxima: bad argument");
-  afh_an::Ctx c;
-  if (int32_t e = an_ctx(t, (size_t)4 * n_max, "afh_tree_local_maxima", c)) return e;
-  AFH_HIP(afh_an::maxima(c, t->ccv(iv), afh_an::geo_cc(3, t->nc, t->bsz), threshold, n_max,
-                         coord_val, n_found));
-  return AFH_OK;
+  return afh_an::local_maxima<3>(t, iv, threshold, n_max, coord_val, n_found);
 }
 
 int32_t afh_tree_fetch_reduced(afh_tree *t, int32_t n, const int32_t *slots, double *out) {
@@ -1621,18 +1461,6 @@ int32_t afh_plan_unpack(afh_tree *t, int32_t plan, int32_t iv,
     t->touch(iv);
   return plan_copy(t, plan, iv, const_cast<double *>(buf), 1);
 }
-
-}  // extern "C"
-
-// device id list for one launch (freed by the caller after a sync)
-static int32_t device_list(const std::vector<int32_t> &h, int32_t **d) {
-  AFH_HIP(hipMalloc(d, sizeof(int32_t) * std::max<size_t>(1, h.size())));
-  if (!h.empty())
-    AFH_HIP(hipMemcpy(*d, h.data(), sizeof(int32_t) * h.size(), hipMemcpyHostToDevice));
-  return AFH_OK;
-}
-
-extern "C" {
 
 int32_t afh_set_cc_prolong(afh_tree *t, int32_t iv, int32_t method, int32_t limiter) {
   if (t) t->meth_gen++;

@@ -31,6 +31,33 @@ def test_oracle_exports_same_api():
     assert not missing, missing
 
 
+@pytest.mark.parametrize("which", ["3d", "2d"])
+def test_bad_argument_sets_the_error_text(which):
+    """The error plumbing both libraries share: a null handle returns
+    AFH_ERR_ARG (-1) and afh_last_error() gives the call's text, the next
+    failing call replaces it. No GPU: the handles are refused before any
+    device call. (afh_profile_read's text differs between the libraries.)"""
+    lib = ctypes.CDLL(capi.HIP_LIB if which == "3d" else capi.HIP_LIB_2D)
+    lib.afh_last_error.restype = ctypes.c_char_p
+    fn = lib.afh_fluid_set_source_factor
+    fn.restype = ctypes.c_int32
+    fn.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_double,
+                   ctypes.c_int32]
+    assert fn(None, 0, None, 0.0, 0) == -1
+    assert lib.afh_last_error() == b"afh_fluid_set_source_factor: null"
+    out = ctypes.c_double()
+    lib.afh_tree_sum_cc.restype = ctypes.c_int32
+    lib.afh_tree_sum_cc.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
+                                    ctypes.c_void_p]
+    assert lib.afh_tree_sum_cc(None, 1, 1, ctypes.byref(out)) == -1
+    assert lib.afh_last_error() == b"afh_tree_sum_cc: null tree"
+    lib.afh_profile_read.restype = ctypes.c_int32
+    lib.afh_profile_read.argtypes = [ctypes.c_void_p] * 4
+    assert lib.afh_profile_read(None, None, None, None) == -1
+    assert lib.afh_last_error() == (b"null argument" if which == "3d"
+                                    else b"afh_profile_read: null argument")
+
+
 def test_no_device_is_an_error_not_a_fallback():
     """Without a GPU the product must fail loudly (no CPU fallback)."""
     import numpy as np
