@@ -11,6 +11,8 @@
 //   k_corr_tmp      correct_children part 1: tmp = phi - tmp (636-637)
 //   k_prolong       stencil_prolong_248 add (m_af_stencil.f90:749-771)
 //   k_gradient      mg_box_lpl_gradient + mg_box_field_norm (1882-2025)
+//   k_residual_flat, k_prolong_flat   the same two passes on boxes of even
+//                   nc >= 32, swept flat in 16-byte aligned pairs (AFH_MG_FLAT)
 // plus the level-1 coarse solver (ours; the reference calls HYPRE PFMG).
 #include <hip/hip_ext.h>
 
@@ -1234,6 +1236,144 @@ __global__ void __launch_bounds__(256)
   if (MAX) block_max_to_shard(mx, red);
 }
 
+// Two cells of a box image that start on a 16-byte boundary. For even nc the
+// row stride nc + 2, the plane stride and bsz are even, so with a 16-byte
+// aligned pool elements (2p, 2p + 1) of the flat image are such a pair, and
+// so are their y and z neighbours: one global_load_dwordx4 each.
+typedef double dbl2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ dbl2 ld2(const double *p) {
+  return *reinterpret_cast<const dbl2 *>(p);
+}
+
+// The interior cells of the aligned pair (vx, vy) at p: both as 16 bytes, or
+// the one of a row's first / last pair as 8; its ghost cell keeps its value.
+template <bool NT>
+__device__ __forceinline__ void st_pair(double *p, double vx, double vy, bool sx, bool sy) {
+  if (sx && sy) {
+    const dbl2 v = {vx, vy};
+    if constexpr (NT) __builtin_nontemporal_store(v, reinterpret_cast<dbl2 *>(p));
+    else *reinterpret_cast<dbl2 *>(p) = v;
+  } else if (sx) {
+    st_nt<NT>(p, vx);
+  } else if (sy) {
+    st_nt<NT>(p + 1, vy);
+  }
+}
+
+// Thread t of a flat sweep over the ghosted planes of a box in aligned pairs,
+// a column of K planes each: column block kq (planes kq K + 1 ..), pair p of
+// the plane = pair m of row j (0 .. nc + 1). Threads past the end take the
+// last pair and are not live (they still load, in bounds, and shuffle).
+struct FlatPair {
+  unsigned kq, p, j, m;
+  bool live;
+};
+__device__ __forceinline__ FlatPair flat_pair(int nc, int K) {
+  const unsigned hw = (nc + 2) >> 1, npp = hw * (nc + 2), total = npp * (nc / K);
+  const unsigned t0 = blockIdx.x * blockDim.x + threadIdx.x;
+  FlatPair f;
+  f.live = t0 < total;
+  const unsigned t = f.live ? t0 : total - 1;
+  f.kq = t / npp;
+  f.p = t - f.kq * npp;
+  f.j = f.p / hw;
+  f.m = f.p - f.j * hw;
+  return f;
+}
+
+// k_residual on boxes of even nc in 16-byte aligned pools, swept flat over the
+// whole ghosted plane: every load of phi and rhs is an aligned pair, 1 KB per
+// wave instruction, 2.25 of them per cell with K = 4 instead of 6.25 8-byte
+// loads. The x neighbours of a pair are the adjacent lanes' (__shfl_up /
+// __shfl_down); lanes 0 and 63 load theirs (8 bytes). Ghost rows compute and
+// store nothing (their y neighbours lie in the planes k -+ 1 of the box
+// image, so no address leaves it); ghost cells of tmp and nrm keep their
+// values. The expressions are k_residual's: bitwise the same results.
+template <bool MAX, int K, bool GRAD = false>
+__global__ void __launch_bounds__(256)
+    k_residual_flat(const double *__restrict__ phi, const double *__restrict__ rhs,
+                    double *__restrict__ tmp, const int32_t *__restrict__ ids, int nc,
+                    size_t bsz, Coef cf0, unsigned long long *red,
+                    const Coef *__restrict__ cft = nullptr,
+                    const afh_box_meta *__restrict__ meta = nullptr,
+                    double *__restrict__ nrm = nullptr, double gfac = 0.0) {
+  const FlatPair f = flat_pair(nc, K);
+  const int id = ids[blockIdx.y];
+  const Coef cf = cft ? cft[meta[id - 1].lvl - 1] : cf0;
+  const int ng = nc + 2;
+  const size_t sj = ng, sk = (size_t)ng * ng;
+  const size_t o = (size_t)(id - 1) * bsz, c0 = (size_t)(f.kq * K + 1) * sk + 2 * (size_t)f.p;
+  const double *x = phi + o;
+  const int lane = threadIdx.x & 63;
+  dbl2 z[K + 2], ym[K], yp[K], r[K];
+  double e[K];
+#pragma unroll
+  for (int q = 0; q < K + 2; q++) z[q] = ld2(x + (c0 + q * sk - sk));
+#pragma unroll
+  for (int q = 0; q < K; q++) {
+    const size_t c = c0 + q * sk;
+    ym[q] = ld2(x + (c - sj));
+    yp[q] = ld2(x + (c + sj));
+    r[q] = ld2(rhs + (o + c));
+  }
+  // the cell before the wave's first pair, the cell after its last one
+  // (planes 1 .. nc: both inside the box image)
+  if (lane == 0 || lane == 63) {
+    const size_t ce = lane ? c0 + 2 : c0 - 1;
+#pragma unroll
+    for (int q = 0; q < K; q++) e[q] = x[ce + q * sk];
+  } else {
+#pragma unroll
+    for (int q = 0; q < K; q++) e[q] = 0.0;
+  }
+  const bool row = f.live && f.j >= 1 && f.j <= (unsigned)nc;
+  const bool sx = row && f.m >= 1, sy = row && f.m < (unsigned)(nc >> 1);
+  double xl[K], xr[K], mx = 0.0;
+#pragma unroll
+  for (int q = 0; q < K; q++) {
+    const double l = __shfl_up(z[q + 1].y, 1), h = __shfl_down(z[q + 1].x, 1);
+    xl[q] = lane == 0 ? e[q] : l;
+    xr[q] = lane == 63 ? e[q] : h;
+  }
+#pragma unroll
+  for (int q = 0; q < K; q++) {
+    // apply7 operand order
+    const double ax = cf.c[0] * z[q + 1].x + cf.c[1] * xl[q] + cf.c[2] * z[q + 1].y +
+                      cf.c[3] * ym[q].x + cf.c[4] * yp[q].x + cf.c[5] * z[q].x +
+                      cf.c[6] * z[q + 2].x;
+    const double ay = cf.c[0] * z[q + 1].y + cf.c[1] * z[q + 1].x + cf.c[2] * xr[q] +
+                      cf.c[3] * ym[q].y + cf.c[4] * yp[q].y + cf.c[5] * z[q].y +
+                      cf.c[6] * z[q + 2].y;
+    const double vx = r[q].x - ax, vy = r[q].y - ay;
+    st_pair<AFH_NT_MG>(tmp + (o + c0 + q * sk), vx, vy, sx, sy);
+    if (sx) mx = fmax(mx, fabs(vx));
+    if (sy) mx = fmax(mx, fabs(vy));
+  }
+  if constexpr (GRAD) {
+    const afh_box_meta &mb = meta[id - 1];
+    const double gx = gfac / mb.dr[0], gy = gfac / mb.dr[1], gz = gfac / mb.dr[2];
+#pragma unroll
+    for (int q = 0; q < K; q++) {
+      double n2[2];
+#pragma unroll
+      for (int s = 0; s < 2; s++) {
+        const double pv = s ? z[q + 1].y : z[q + 1].x;
+        const double pxm = s ? z[q + 1].x : xl[q], pxp = s ? xr[q] : z[q + 1].y;
+        const double pym = s ? ym[q].y : ym[q].x, pyp = s ? yp[q].y : yp[q].x;
+        const double pzm = s ? z[q].y : z[q].x, pzp = s ? z[q + 2].y : z[q + 2].x;
+        const double fxl = gx * (pv - pxm), fxh = gx * (pxp - pv);
+        const double fyl = gy * (pv - pym), fyh = gy * (pyp - pv);
+        const double fzl = gz * (pv - pzm), fzh = gz * (pzp - pv);
+        const double a = fxl + fxh, b = fyl + fyh, c = fzl + fzh;
+        n2[s] = 0.5 * sqrt(a * a + b * b + c * c);
+      }
+      st_pair<AFH_NT_MG>(nrm + (o + c0 + q * sk), n2[0], n2[1], sx, sy);
+    }
+  }
+  if (MAX) block_max_to_shard(mx, red);
+}
+
 // update_coarse part 1, one thread per parent cell (the column form below
 // serves the constant boxes whose size allows it)
 template <class St>
@@ -1692,6 +1832,65 @@ __global__ void __launch_bounds__(256)
                          (9 / 64.0) * pv[a][2] + (3 / 64.0) * pv[a][3] +
                          (9 / 64.0) * pv[b][0] + (3 / 64.0) * pv[b][1] +
                          (3 / 64.0) * pv[b][2] + (1 / 64.0) * pv[b][3]);
+  }
+}
+
+// k_prolong in the flat form of k_residual_flat (same boxes, same mapping):
+// phi is read and written as aligned pairs. The two cells of a pair, i = 2m
+// and 2m + 1, take the same two parent columns o0 + m and o0 + m + 1 with
+// the weights swapped, so a parent plane's four values serve both cells:
+// half the parent loads per cell. Expression and operand order of k_prolong
+// for each cell; ghost cells are not written.
+template <int K>
+__global__ void __launch_bounds__(256)
+    k_prolong_flat(double *__restrict__ phi, const double *__restrict__ tmp,
+                   const afh_box_meta *__restrict__ meta,
+                   const int32_t *__restrict__ ids, int nc, size_t bsz) {
+  const FlatPair f = flat_pair(nc, K);
+  const int id = ids[blockIdx.y];
+  const afh_box_meta &mb = meta[id - 1];
+  const int k0 = f.kq * K + 1;  // odd
+  const int ng = nc + 2, hn = nc >> 1, j = f.j;
+  const size_t sk = (size_t)ng * ng;
+  const int o0 = ((mb.ix[0] - 1) & 1) * hn, o1 = ((mb.ix[1] - 1) & 1) * hn,
+            o2 = ((mb.ix[2] - 1) & 1) * hn;
+  // cell 2m: (i1, i2) = (ia, ia + 1); cell 2m + 1: (ia + 1, ia). On the
+  // ghost rows and in the ghost cells of a row's end pairs the parent
+  // indices stay inside 0 .. nc + 1
+  const int ia = o0 + f.m;
+  const int j1 = o1 + ((j + 1) >> 1), j2 = j1 + 1 - 2 * (j & 1);
+  const int P = o2 + ((k0 + 1) >> 1);
+  const double *p = tmp + (size_t)(mb.parent - 1) * bsz;
+  const size_t c = (size_t)(id - 1) * bsz + (size_t)k0 * sk + 2 * (size_t)f.p;
+  // parent planes P-1 .. P+K/2, values at (ia,j1), (ia+1,j1), (ia,j2), (ia+1,j2)
+  double pv[K / 2 + 2][4];
+  dbl2 ph[K];
+#pragma unroll
+  for (int q = 0; q < K / 2 + 2; q++) {
+    const size_t b = ix3(ng, 0, 0, P - 1 + q);
+    pv[q][0] = p[b + (size_t)j1 * ng + ia];
+    pv[q][1] = p[b + (size_t)j1 * ng + ia + 1];
+    pv[q][2] = p[b + (size_t)j2 * ng + ia];
+    pv[q][3] = p[b + (size_t)j2 * ng + ia + 1];
+  }
+#pragma unroll
+  for (int q = 0; q < K; q++) ph[q] = ld2(phi + (c + q * sk));
+  const bool row = f.live && j >= 1 && j <= nc;
+  const bool sx = row && f.m >= 1, sy = row && f.m < (unsigned)hn;
+#pragma unroll
+  for (int q = 0; q < K; q++) {
+    // planes of cell k0+q as in k_prolong
+    const int a = (q & 1) ? (q + 1) / 2 : q / 2 + 1;
+    const int b = (q & 1) ? (q + 3) / 2 : q / 2;
+    const double vx = ph[q].x + (27 / 64.0) * pv[a][0] + (9 / 64.0) * pv[a][1] +
+                      (9 / 64.0) * pv[a][2] + (3 / 64.0) * pv[a][3] +
+                      (9 / 64.0) * pv[b][0] + (3 / 64.0) * pv[b][1] +
+                      (3 / 64.0) * pv[b][2] + (1 / 64.0) * pv[b][3];
+    const double vy = ph[q].y + (27 / 64.0) * pv[a][1] + (9 / 64.0) * pv[a][0] +
+                      (9 / 64.0) * pv[a][3] + (3 / 64.0) * pv[a][2] +
+                      (9 / 64.0) * pv[b][1] + (3 / 64.0) * pv[b][0] +
+                      (3 / 64.0) * pv[b][3] + (1 / 64.0) * pv[b][2];
+    st_pair<AFH_NT_MG>(phi + (c + q * sk), vx, vy, sx, sy);
   }
 }
 
@@ -2703,6 +2902,9 @@ struct afh_mg {
   int rstr_k = AFH_RSTR_K;     // coarse cells per column (AFH_RSTR_K=2|4|8 at run time)
   int res_k = AFH_RES_K;       // residual cells per column (AFH_RES_K=2|4|8 at run time)
   int prolong_k = 4;           // prolongation cells per column (AFH_PROLONG_K=2|4|8)
+  // AFH_MG_FLAT: residual and correction of constant boxes of even nc >= 32
+  // as flat sweeps in aligned pairs (k_residual_flat, k_prolong_flat)
+  bool flat = true;
   int rstr_bs = 256;           // k_rstr_fas_col workgroup size
   int wave_cells = CS_WAVE_CELLS;
   // AFH_COARSE_DIRECT: eigenvectors Q and Q^T per dim, eigenvalues, work
@@ -3015,6 +3217,7 @@ int32_t afh_mg_create(afh_tree *t, const afh_mg_desc *d, afh_mg **out) {
     mg->res_k = atoi(env) == 8 ? 8 : atoi(env) == 2 ? 2 : 4;
   if (const char *env = getenv("AFH_PROLONG_K"))
     mg->prolong_k = atoi(env) == 8 ? 8 : atoi(env) == 2 ? 2 : 4;
+  if (const char *env = getenv("AFH_MG_FLAT")) mg->flat = atoi(env) != 0;
   if (const char *env = getenv("AFH_CS_ELEC_DIRECT")) mg->csd_on = atoi(env) != 0;
   if (const char *env = getenv("AFH_CS_DIRECT_SMALL")) mg->cs_direct_small = atoi(env) != 0;
   if (const char *env = getenv("AFH_GSRB_TILES_MIN")) mg->tiles_min = atoi(env);
@@ -3481,6 +3684,22 @@ static bool prolong_push(const afh_mg *mg, int lvl) {
          fused_level(mg, lvl);
 }
 
+// the flat forms k_residual_flat / k_prolong_flat apply (AFH_MG_FLAT=0: off):
+// even nc >= 32 (row, plane and box strides even), columns of 4 or 8, and
+// every array of the launch on a 16-byte boundary
+static bool mg_flat(const afh_mg *mg, int k, std::initializer_list<const void *> arrays) {
+  const int nc = mg->t->nc;
+  if (!mg->flat || nc < 32 || (nc & 1) || k < 4 || nc % k) return false;
+  for (const void *p : arrays)
+    if (reinterpret_cast<uintptr_t>(p) & 15) return false;
+  return true;
+}
+
+// blocks of 256 threads of a flat sweep: (nc+2)^2/2 pairs per plane, nc/k columns
+static unsigned flat_blocks(int nc, int k) {
+  return ((unsigned)((nc + 2) * (nc + 2) / 2 * (nc / k)) + 255) / 256;
+}
+
 static int32_t correct_children(afh_mg *mg, int lvl) {
   afh_tree *t = mg->t;
   const int np = t->parents.n(lvl - 1), nc = t->nc;
@@ -3507,12 +3726,20 @@ static int32_t correct_children(afh_mg *mg, int lvl) {
     // 13.32 against 12.57-12.60 ms per step (profiles/r03_ab_prolong_k.txt)
     const int want = mg->prolong_k;
     const int K = want == 8 && nc % 8 == 0 ? 8 : want >= 4 && nc % 4 == 0 ? 4 : 2;
-    const dim3 grid((nc * nc * (nc / K) + 255) / 256, nid);
+    const bool flat = mg_flat(mg, K, {fphi, t->ccv(mg->d.i_tmp)});
+    const dim3 grid(flat ? flat_blocks(nc, K) : (nc * nc * (nc / K) + 255) / 256, nid);
     with_col(K, [&](auto K_) {
-      hipLaunchKernelGGL(k_prolong<decltype(K_)::value>, grid, dim3(256), 0, t->stream, fphi,
+      constexpr int KC = decltype(K_)::value;
+      if constexpr (KC >= 4)
+        if (flat) {
+          hipLaunchKernelGGL(k_prolong_flat<KC>, grid, dim3(256), 0, t->stream, fphi,
+                             t->ccv(mg->d.i_tmp), t->d_boxes, t->ids.at(lvl), nc, t->bsz);
+          return;
+        }
+      hipLaunchKernelGGL(k_prolong<KC>, grid, dim3(256), 0, t->stream, fphi,
                          t->ccv(mg->d.i_tmp), t->d_boxes, t->ids.at(lvl), nc, t->bsz);
     });
-    AFH_LAUNCH_CHECK("k_prolong");
+    AFH_LAUNCH_CHECK(flat ? "k_prolong_flat" : "k_prolong");
   }
   return AFH_OK;
 }
@@ -4166,7 +4393,14 @@ static int32_t residual_levels(afh_mg *mg, int max_lvl, bool max_out) {
   // columns of 8 on the large boxes: 693 against 728 us per 64^3 leaf
   // launch (profiles/r03_ab_res_k.txt); small boxes keep their threads
   const int rk = mg->res_k ? mg->res_k : nc >= 32 ? 8 : 4;
-  const int kc = nc % rk == 0 ? rk : nc % 4 == 0 ? 4 : 2;
+  int kc = nc % rk == 0 ? rk : nc % 4 == 0 ? 4 : 2;
+  // the flat form on aligned pairs; without AFH_RES_K its columns are 4 long:
+  // 983 against 1015 us per 64^3 leaf launch with 8 (122 VGPRs and 4 waves
+  // per SIMD against 210 and 2; profiles/mg_flat_steady_s1-64.json)
+  const double *gnrm = gr ? t->ccv(mg->grad_iv) : nullptr;
+  const bool flat = mg_flat(mg, kc, {t->ccv(mg->d.i_phi), t->ccv(mg->d.i_rhs),
+                                     t->ccv(mg->d.i_tmp), gnrm});
+  if (flat && !mg->res_k) kc = 4;
   for (int lvl = 1; lvl <= max_lvl; lvl++) {
     for (int part = 0; part < 2; part++) {
       // part 0: leaves (max folded), part 1: parents; without max_out the
@@ -4188,16 +4422,26 @@ static int32_t residual_levels(afh_mg *mg, int max_lvl, bool max_out) {
           else
             with_bool(gr, [&](auto GR) {
               with_col(kc, [&](auto K) {
+                constexpr int KC = decltype(K)::value;
+                const Coef *cft = one ? mg->d_lvl_c : nullptr;
+                const afh_box_meta *meta = (one || GR) ? t->d_boxes : nullptr;
+                double *nrm = GR ? t->ccv(mg->grad_iv) : nullptr;
+                if constexpr (KC >= 4)
+                  if (flat) {
+                    hipLaunchKernelGGL(
+                        (k_residual_flat<decltype(MX)::value, KC, decltype(GR)::value>),
+                        dim3(flat_blocks(nc, KC), n), dim3(256), 0, t->stream, phi, rhs, tmp,
+                        L.at(lvl), nc, t->bsz, st.cf, red, cft, meta, nrm, mg->grad_fac);
+                    return;
+                  }
                 hipLaunchKernelGGL(
-                    (k_residual<decltype(MX)::value, decltype(K)::value, decltype(GR)::value>),
+                    (k_residual<decltype(MX)::value, KC, decltype(GR)::value>),
                     dim3((n3 / K + 255) / 256, n), dim3(256), 0, t->stream, phi, rhs, tmp,
-                    L.at(lvl), nc, t->bsz, st.cf, red, one ? mg->d_lvl_c : nullptr,
-                    (one || GR) ? t->d_boxes : nullptr, GR ? t->ccv(mg->grad_iv) : nullptr,
-                    mg->grad_fac);
+                    L.at(lvl), nc, t->bsz, st.cf, red, cft, meta, nrm, mg->grad_fac);
               });
             });
         });
-        AFH_LAUNCH_CHECK(is_var<St> ? "k_residual_v" : "k_residual");
+        AFH_LAUNCH_CHECK(is_var<St> ? "k_residual_v" : flat ? "k_residual_flat" : "k_residual");
         return AFH_OK;
       };
       const LevelList *all[] = {&t->ids, &t->leaves, &t->parents},

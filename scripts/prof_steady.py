@@ -60,8 +60,14 @@ def rules(topo):
         (r"k_residual<false, \d, true", 32, "parents", None),
         (r"k_residual<true", 24, "leaves", None),
         (r"k_residual<false", 24, "parents", None),
+        # the flat forms on aligned pairs (AFH_MG_FLAT): the same passes
+        (r"k_residual_flat<true, \d, true", 32, "leaves", None),
+        (r"k_residual_flat<false, \d, true", 32, "parents", None),
+        (r"k_residual_flat<true", 24, "leaves", None),
+        (r"k_residual_flat<false", 24, "parents", None),
         (r"k_rstr_fas", 18, "ids", None),
         (r"k_prolong<", 20, "ids", None),
+        (r"k_prolong_flat<", 20, "ids", None),
         (r"k_corr_tmp", 24, "parents", None),
         (r"k_parent_rhs", 24, "parents", None),
         # with the face field formed in the flux (faces_from_phi): the
@@ -102,7 +108,7 @@ def key(name):
 
 # kernels whose grid is (cells of a box, boxes): one launch may cover every
 # leaf level (AFH_ALL_LVL), so the boxes are read from the launch's grid
-BOX_GRID = re.compile(r"k_update<|k_flux_staged|k_residual<")
+BOX_GRID = re.compile(r"k_update<|k_flux_staged|k_residual<|k_residual_flat<")
 # the fused pair's grid is (boxes x NC/TJ row tiles x KS k-splits) workgroups
 # (afh_mg.hip launch_pair2): its boxes follow from the launch's workgroups
 PAIR2 = re.compile(r"k_gsrb_pair2<(\d+), (\d+), \d+, (\d+)>")
